@@ -14,6 +14,17 @@ WORLD_SIZE spawns the N local ranks itself (child processes with RANK/LOCAL_RANK
 127.0.0.1 rendezvous, started before this process touches the GPU) and exits with the worst child
 status.  Either way the run fails unless the process group has exactly --gpus ranks.
 
+A plain run sets up, warms up, times --steps steps and prints the result line (value, ms_per_step,
+sample counts, config).  `--full` adds, after the timed steps, everything else the benchmark
+measures: the compositor's roofline launches, the per-kernel table, the other MLP precision, the
+trained states, the test-time render, config #5's preset and the CPU baseline.
+`--dump-outputs DIR` writes what the timed path's step returns as DIR/<name>.npy (dump_arrays): the
+last timed step's batch and step number, run once more after the clock has stopped from the seeded
+state the steps started from.  The inputs depend on the arguments alone and one step from them is
+reproducible up to the atomics of the table gradient (~5e-8 on the parameters), so two builds can
+be compared output for output; the state the timed steps themselves leave differs from run to run
+(training amplifies that rounding from step to step).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -106,6 +117,49 @@ def window_start(base, warmup, steps, every=16):
         if count(s0 + warmup) == want:
             return s0, want
     return base, count(base + warmup)
+
+
+DUMP_MAX_ELEMS = 1 << 21  # per array (8 MB as float32); the arrays of a dump together stay far below 64 MB
+DUMP_SAMPLES_PER_RAY = 128  # columns of the per-sample arrays (the bench's rays hold ~70 samples on average)
+
+
+def dump_arrays(results, loss_d, params):
+    """What a Trainer.step returned, and the flat parameters after it, as host
+    arrays for --dump-outputs (float32; the integer counts as float64):
+      rgb, opacity, depth, total_samples, n_samples: per ray, in ray order (total_samples: the samples
+        the compositor integrated; n_samples: the samples the marcher placed);
+      deltas, ts, ws: per sample, (rays, DUMP_SAMPLES_PER_RAY): row r holds ray r's first samples in
+        marching order, 0 behind its last one (the marcher's own row order puts the long rays first,
+        and the number of samples changes from step to step: the shapes here depend on the arguments
+        alone); ws is also 0 past a ray's total_samples, where the compositor leaves its rows
+        unwritten;
+      loss_<term>: the loss terms (one element each);
+      params: the model's flat parameters after the step's optimizer.
+    An array of more than DUMP_MAX_ELEMS elements is stored as a fixed sample of its elements
+    (sorted indices drawn by a generator seeded with the array's size)."""
+    host = lambda t: t.detach().cpu().numpy()  # noqa: E731
+    ra = host(results["rays_a"]).astype(np.int64)  # rows of (ray, first sample row, samples)
+    ra = ra[np.argsort(ra[:, 0], kind="stable")]
+    n = ra[:, 2]
+    total = next(host(results[k]) for k in ("total_samples", "vr_samples")
+                 if k in results and results[k].numel() == ra.shape[0]).astype(np.int64)
+    pos = np.arange(DUMP_SAMPLES_PER_RAY)[None, :]  # a sample's index within its ray
+    placed = pos < n[:, None]
+    rows = np.where(placed, ra[:, 1:2] + pos, 0)
+    out = {k: host(results[k]) for k in ("rgb", "opacity", "depth")}
+    out["total_samples"], out["n_samples"] = total, n
+    for k in ("deltas", "ts", "ws"):
+        out[k] = np.where(placed, host(results[k])[rows], np.float32(0))
+    out["ws"] = np.where(pos < total[ra[:, 0], None], out["ws"], np.float32(0))
+    for k, v in loss_d.items():
+        out["loss_" + k] = host(v).reshape(1)
+    out["params"] = host(params)
+    for k, v in out.items():
+        v = np.ascontiguousarray(v, dtype=np.float32 if v.dtype == np.float32 else np.float64)
+        if v.size > DUMP_MAX_ELEMS:
+            v = v.reshape(-1)[np.sort(np.random.default_rng(v.size).choice(v.size, DUMP_MAX_ELEMS, replace=False))]
+        out[k] = v
+    return out
 
 
 def pmc_traffic():
@@ -415,7 +469,15 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rays", type=int, default=8192, help="rays per GPU per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement also run the roofline launches, the per-kernel table, the "
+                         "other-precision, trained-state, eval-render and other-config lines and the CPU baseline "
+                         "(each of them can be switched off with its --no-... option); without --full only the "
+                         "headline steps are run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path's step returns from the seeded state (and "
+                         "the parameters after it) as DIR/<name>.npy (rank 0; dump_arrays)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline legs")
     ap.add_argument("--no-grid-update", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="eager (Python-launched) step instead of a HIP graph")
     ap.add_argument("--no-defer", action="store_true",
@@ -476,7 +538,7 @@ def main():
 
     GT = "surface_bright"  # synthetic target colours (ncnerf_amd.synthetic)
 
-    def measure(precision, steps, kernel_table, pretrain, state="procedural", preset="hypersim"):
+    def measure(precision, steps, kernel_table, pretrain, state="procedural", preset="hypersim", dump=False):
         """Build the model in `precision`, pretrain it `pretrain` untimed steps, warm up, time `steps`
         graph-replayed training steps (barrier + synchronize on both sides), max over ranks.
         state "procedural": the procedural occupancy grid (BASELINE.md §2), fixed while pretraining;
@@ -519,6 +581,21 @@ def main():
             n_refresh = 0
         if trainer.update_grid and state != "refreshed":  # first-call costs of the refresh path stay out of the timed region
             model.update_density_grid(0.01 * 1024 / 3 ** 0.5, warmup=False)
+
+        def state():
+            """Every tensor a training step or a grid refresh changes, and the optimizer's step count."""
+            tensors = trainer.opt.state_tensors() + [model.flat_grad(), model.density_grid, model.density_bitfield]
+            return [t.clone() for t in tensors], trainer.opt.step_count
+
+        def set_state(saved):
+            trainer.flush_optimizer()
+            tensors = trainer.opt.state_tensors() + [model.flat_grad(), model.density_grid, model.density_bitfield]
+            for t, v in zip(tensors, saved[0]):
+                t.copy_(v)
+            trainer.opt.step_count = saved[1]
+            model.prepare_weights()  # (the MLP fragments of the restored parameters)
+
+        seeded = state() if dump else None  # the state all the steps start from: a function of the arguments
         for k in range(args.warmup):
             trainer.step(batches[k % n_batches], global_step=step0 + k)
         trainer.flush_optimizer()  # (the timed region holds exactly `steps` optimizer steps)
@@ -538,6 +615,26 @@ def main():
             dist.barrier()
         t1 = time.perf_counter()
         tot = count_acc.clone()
+        if dump:
+            # --dump-outputs: the timed path's step (the last timed step's batch and step number) run once
+            # more, now that the clock has stopped, from the seeded state.  The state the timed steps
+            # themselves leave is not the same in every run: the table gradient is summed with float
+            # atomics (~5e-8 on the parameters after one step), and training amplifies that from step to
+            # step (clustering labels, the grid refresh's threshold: 0.15 after 25 steps), so their last
+            # outputs say nothing about a build.  From the seeded state one step is reproducible to that
+            # rounding.  The state of the timed steps is put back afterwards.
+            trained, refresh = state(), trainer.update_grid
+            set_state(seeded)
+            trainer.update_grid = False  # (the seeded grid, whatever the step number)
+            k = args.warmup + max(steps, 1) - 1
+            last = trainer.step(batches[k % n_batches], global_step=step0 + k)
+            trainer.flush_optimizer()
+            torch.cuda.synchronize()
+            dump = dump_arrays(*last, model.flat_params()) if rank == 0 else None
+            set_state(trained)
+            trainer.update_grid = refresh
+        else:
+            dump = None
         if not args.no_graph and kernel_table:
             # Per-kernel durations (the `kernels` table): a graph replay has no host launch to bracket,
             # so the captured body is run eagerly for `steps` more steps with HIP events on the launch
@@ -560,9 +657,14 @@ def main():
             dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
             dist.all_reduce(tot, op=dist.ReduceOp.SUM)
         return dict(el=float(elapsed.item()), tot=tot, rank_ms=rank_ms, timing=timing, model=model, batches=batches,
-                    distill=distill, n_refresh=n_refresh)
+                    distill=distill, n_refresh=n_refresh, dump=dump)
 
-    main_run = measure(args.precision, args.steps, True, args.pretrain)
+    main_run = measure(args.precision, args.steps, args.full, args.pretrain, dump=args.dump_outputs is not None)
+    if main_run["dump"] is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in main_run["dump"].items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+        log(f"wrote {len(main_run['dump'])} arrays to {args.dump_outputs}")
     el, tot, rank_ms, timing = main_run["el"], main_run["tot"], main_run["rank_ms"], main_run["timing"]
     model, batches = main_run["model"], main_run["batches"]
     n_refresh = main_run["n_refresh"]
@@ -571,13 +673,16 @@ def main():
         if evs:
             ms = [a.elapsed_time(b) for a, b in evs]
             kern[name] = {"avg_us": round(1e3 * float(np.mean(ms)), 2), "launches": len(ms)}
-    log(f"main run: {args.rays * world * args.steps / el:.1f} rays/s; roofline launches")
-    cf_bytes_per_launch, cf_t = composite_fw_roofline(model, batches, dev, SyntheticScene())
-    cf_us = cf_t["hbm"]
-    traffic, traffic_src = pmc_traffic()
+    log(f"main run: {args.rays * world * args.steps / el:.1f} rays/s")
+    if args.full:
+        log("roofline launches")
+        cf_bytes_per_launch, cf_t = composite_fw_roofline(model, batches, dev, SyntheticScene())
+        cf_us = cf_t["hbm"]
+        traffic, traffic_src = pmc_traffic()
     del main_run, model, batches
     second = None
-    if not args.no_bf16_line:  # the same step with the other MLP operand type (configs[2] asks for bf16)
+    # the same step with the other MLP operand type (configs[2] asks for bf16)
+    if args.full and not args.no_bf16_line:
         prec2 = "bf16" if args.precision == "fp16" else "fp16"
         r2 = measure(prec2, args.steps, False, args.pretrain)
         second = {"precision": prec2, "value": round(args.rays * world * args.steps / r2["el"], 1), "unit": "rays/s",
@@ -587,7 +692,7 @@ def main():
                               "-operand MFMA in the field MLP"}
         del r2
     extra = {}
-    if not args.no_extra_states:
+    if args.full and not args.no_extra_states:
         for key, pre, st, what in (
                 ("init_state", 0, "procedural", "random-init NGPMT on the procedural occupancy grid: rays never "
                                                 "terminate early"),
@@ -631,7 +736,6 @@ def main():
                                  "workload": "configs[4]'s hyper-parameters (experiments/scannet_man/hyperparameters.py:"
                                              " loss_norm_D_C_* = 1e-2) on the synthetic Hypersim-shaped inputs"}
         del r5
-    achieved = cf_bytes_per_launch / (cf_us * 1e-6) / 1e9
     if rank != 0:
         if world > 1:
             dist.destroy_process_group()
@@ -674,40 +778,42 @@ def main():
         "vr_samples_per_s": round(float(tot[1].item()) / el, 1),
         "rm_samples_per_ray": round(float(tot[0].item()) / rays_total, 2),
         "vr_samples_per_ray": round(float(tot[1].item()) / rays_total, 2),
-        "roofline": {"kernel": "composite_train_fw (ncn_composite_train_fw_bg, the step's compositor)",
-                     "bound": "hbm", "achieved": round(achieved, 1),
-                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                     "frac_of_measured_copy": round(achieved / HBM_COPY_GBS, 4),
-                     "measured_copy_gbs": HBM_COPY_GBS,
-                     "traffic": traffic, "traffic_source": traffic_src,
-                     "algorithmic_bytes_per_launch": round(cf_bytes_per_launch),
-                     "avg_launch_us": round(cf_us, 2),
-                     "warm_us": round(cf_t["warm"], 2),
-                     "frac_warm": round(cf_t["warm_bytes"] / (cf_t["warm"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
-                     "in_step_us": round(cf_t["in_step"], 2),
-                     "batch65536": {"avg_launch_us": round(cf_t["big_us"], 2),
-                                    "algorithmic_bytes_per_launch": round(cf_t["big_bytes"]),
-                                    "frac": round(cf_t["big_bytes"] / (cf_t["big_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
-                                    "method": "one launch over config #4's global batch (65536 rays), 12 launches "
-                                              "cycling through 3 sets of ~140 MB (HBM-cold), HIP events around all"},
-                     "single_launch_floor": {"us": 5.1, "frac": 0.41,
-                                             "note": "a load-only kernel of the same grid over the same ~19 MB "
-                                                     "(round 4, DESIGN section 7): the launch ramp plus one round "
-                                                     "of loads at ~6.3 TB/s bound one 8192-ray launch at ~0.41 of "
-                                                     "the 8 TB/s spec before any arithmetic"},
-                     "method": "avg_launch_us (-> achieved, frac): 48 back-to-back launches cycling through 24 "
-                               "input sets (~16.5 MB each, ~400 MB in all, ~1.5x the 256 MiB Infinity Cache, so "
-                               "each set is evicted before it is read again), HIP events on the launch stream "
-                               "around all of them behind a GPU spin; "
-                               "warm_us: the same on one set (cache-resident); in_step_us: one launch right behind "
-                               "the field forward that produced its inputs, its own event pair (launch ramp and "
-                               "event overhead included). Algorithmic bytes 24*S_vr + 4*S + 52*R (SURVEY 8d)"},
-        "kernels": kern,
     }
+    if args.full:
+        achieved = cf_bytes_per_launch / (cf_us * 1e-6) / 1e9
+        roofline = {"kernel": "composite_train_fw (ncn_composite_train_fw_bg, the step's compositor)",
+                    "bound": "hbm", "achieved": round(achieved, 1),
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                    "frac_of_measured_copy": round(achieved / HBM_COPY_GBS, 4),
+                    "measured_copy_gbs": HBM_COPY_GBS,
+                    "traffic": traffic, "traffic_source": traffic_src,
+                    "algorithmic_bytes_per_launch": round(cf_bytes_per_launch),
+                    "avg_launch_us": round(cf_us, 2),
+                    "warm_us": round(cf_t["warm"], 2),
+                    "frac_warm": round(cf_t["warm_bytes"] / (cf_t["warm"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
+                    "in_step_us": round(cf_t["in_step"], 2),
+                    "batch65536": {"avg_launch_us": round(cf_t["big_us"], 2),
+                                   "algorithmic_bytes_per_launch": round(cf_t["big_bytes"]),
+                                   "frac": round(cf_t["big_bytes"] / (cf_t["big_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
+                                   "method": "one launch over config #4's global batch (65536 rays), 12 launches "
+                                             "cycling through 3 sets of ~140 MB (HBM-cold), HIP events around all"},
+                    "single_launch_floor": {"us": 5.1, "frac": 0.41,
+                                            "note": "a load-only kernel of the same grid over the same ~19 MB "
+                                                    "(round 4, DESIGN section 7): the launch ramp plus one round "
+                                                    "of loads at ~6.3 TB/s bound one 8192-ray launch at ~0.41 of "
+                                                    "the 8 TB/s spec before any arithmetic"},
+                    "method": "avg_launch_us (-> achieved, frac): 48 back-to-back launches cycling through 24 "
+                              "input sets (~16.5 MB each, ~400 MB in all, ~1.5x the 256 MiB Infinity Cache, so "
+                              "each set is evicted before it is read again), HIP events on the launch stream "
+                              "around all of them behind a GPU spin; "
+                              "warm_us: the same on one set (cache-resident); in_step_us: one launch right behind "
+                              "the field forward that produced its inputs, its own event pair (launch ramp and "
+                              "event overhead included). Algorithmic bytes 24*S_vr + 4*S + 52*R (SURVEY 8d)"}
+        out["roofline"], out["kernels"] = roofline, kern
     if second is not None:
         out["other_precision"] = second
     out.update(extra)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         log("cpu baseline")
         out["cpu_baseline"] = cpu_baseline()
     print(json.dumps(out))

@@ -5,7 +5,7 @@
 # summarise: python3 tools/pmc_step_summary.py gpurun_out/pmc_step > profiles/<round>/pmc_step.json
 export TMPDIR=/tmp
 out=gpurun_out/pmc_step
-B="python3 bench.py --steps 5 --warmup 3 --no-cpu-baseline --no-bf16-line --no-extra-states"
+B="python3 bench.py --full --steps 5 --warmup 3 --no-cpu-baseline --no-bf16-line --no-extra-states"
 i=0
 for grp in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F16 SQ_INSTS_VALU_MFMA_F16 GRBM_GUI_ACTIVE GRBM_COUNT" "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))

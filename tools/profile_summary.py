@@ -35,7 +35,7 @@ def main(rnd):
     fm, wm = statistics.median(fetch), statistics.median(write)
     out = {"kernel": k, "traffic_bytes_per_launch": int(round((2 * fm + wm) * 1024)),
            "FETCH_SIZE_kb_median": fm, "WRITE_SIZE_kb_median": wm, "dispatches": len(fetch),
-           "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --steps 5` "
+           "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --full --steps 5` "
                      "(graph replays + eager pass + roofline launches), per-dispatch median; gfx950 correction: "
                      "FETCH_SIZE x2 (MI355X_MICROARCH.md HBM), WRITE_SIZE as read; Infinity-Cache hits included"}
     json.dump(out, open(os.path.join(dst, "composite_fw_traffic.json"), "w"), indent=1)
@@ -51,7 +51,7 @@ def main(rnd):
     instep = [dur(r) for i, r in enumerate(rows) if k in r["Kernel_Name"] and i and "field_fwd" in rows[i - 1]["Kernel_Name"]]
     rest = d[:-135]
     live = {"kernel": k + "<3> (ncn_composite_train_fw_bg)",
-            "source": "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 30 --no-cpu-baseline "
+            "source": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 30 --no-cpu-baseline "
                       "--no-bf16-line --no-extra-states (gpurun_out/prof_round/trace)",
             "hbm_cold_48_launches_avg_us": round(statistics.mean(d[-111:-63]), 3),
             "warm_48_launches_avg_us": round(statistics.mean(d[-63:-15]), 3),
