@@ -233,6 +233,16 @@ int ncn_field_pack_map(int32_t* src_index, void* stream);
  * and dE_ws are then in processing order, sigmas / rgbs / dL_d* stay in sample order. */
 int ncn_field_sort_windows(const float* xyzs, int64_t n, const int32_t* n_dev, float xyz_min, float xyz_extent,
                            int32_t* order, void* stream);
+/* Positions outside [xyz_min, xyz_min + xyz_extent] (ncn_field_fwd in every mode, ncn_field_bwd*,
+ * ncn_field_scatter*): no precondition beyond finite coordinates within ~2^20 box widths (the cell
+ * coordinate (uint32)(int)floor(scale * x01 + 0.5) must fit an int32).  They wrap as tiny-cuda-nn's
+ * grid_index does: a negative floor becomes 0xFFFFFFFF.., the dense levels' index x + y * res +
+ * z * res^2 is formed modulo 2^32 and reduced modulo the level's params, the hashed levels' hash is
+ * masked — every table index on every path is reduced before it is used, the grid refresh's x01 == 0
+ * and a marched sample one ulp outside a face included.  The scatter keys a coarse level's cell in
+ * 32 bits only for px, py < 2048 and pz < 1023 and adds the others straight to grad_table.
+ * ncn_field_sort_windows clamps the Morton key's coordinates to [0, 1023] (NaN -> 0).
+ * (tests/test_gpu_field_levels.py) */
 int ncn_field_fwd(const float* xyzs, const float* dirs, int64_t n, const int32_t* n_dev, const int32_t* order,
                   const float* table,
                   const uint32_t* levels, float xyz_min, float xyz_extent, const uint16_t* weights_packed,

@@ -1534,7 +1534,10 @@ __device__ __forceinline__ void sc_drain_cells(ScShared& sh, int lane, const uin
 // is drained first.  Cells outside the key range go straight to global memory.
 __device__ __forceinline__ void sc_push_run(ScShared& sh, int lane, bool fin, const ScRun& st, uint32_t* qk, float4* qv,
                                             int& qn, const ScLevel& L, float* __restrict__ grad) {
-    const bool inkey = st.px < 2048u && st.py < 2048u && st.pz < 1024u;
+    // (pz < 1023: the key of cell (2047, 2047, 1023) would be SC_EMPTY — a lookup would then "find" it
+    // in any empty way, add into a slot that is never claimed nor flushed, and leave the sums behind
+    // for the slot's next owner)
+    const bool inkey = st.px < 2048u && st.py < 2048u && st.pz < 1023u;
     const uint64_t bm = __ballot(fin && inkey);
     if (bm) {
         const int n = (int)__popcll(bm);

@@ -179,7 +179,7 @@ class _RoundST(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, t, dt):
-        return t.to(dt).float()
+        return t.to(dt).to(t.dtype)  # (fp32 callers: as .float(); an fp64 run keeps fp64 accumulation)
 
     @staticmethod
     def backward(ctx, g):
@@ -199,7 +199,7 @@ class _RoundGrad(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        return (g * ctx.K).to(ctx.dt).float() / ctx.K, None, None
+        return (g * ctx.K).to(ctx.dt).to(g.dtype) / ctx.K, None, None
 
 
 def _grad_rounder(emulate, bwd_scale):
@@ -276,7 +276,7 @@ class _TruncExp(torch.autograd.Function):
 
 
 def field_forward_autograd(xyzs, dirs, P, levels, scale=0.5, emulate_f16=False, emulate=None, impl="torch",
-                           bwd_scale=None):
+                           bwd_scale=None, return_enc=False):
     """Same as field_forward with TruncExp's clamped backward, differentiable w.r.t. P.  With
     emulation the forward operands are rounded where the HIP kernel rounds them (the rounding is
     straight-through in the backward), so ReLU masks match the kernel's.  impl: the encoding's
@@ -286,17 +286,29 @@ def field_forward_autograd(xyzs, dirs, P, levels, scale=0.5, emulate_f16=False, 
     gradient (dY5), the pre-ReLU gradients of layers 4, 3 and 1 (dD4, dD3, dD1), dL/dh after the rgb
     path and TruncExp's term are added (dhh), and dL/denc — the fp32 product of those rounded
     operands, stored in the operand type as tcnn hands its network's input gradient to the grid
-    backward; the weight gradients are fp32 products, as the kernel's MFMA accumulates them."""
+    backward; the weight gradients are fp32 products, as the kernel's MFMA accumulates them.
+    return_enc: also return the encoding (N, 32, level-major) with its gradient retained: after the
+    backward its .grad is dL/denc as the grid backward receives it (after the rounding above).
+    The tensors' dtype is kept (every tensor in fp64: the same operand rounding points with fp64
+    accumulation; impl "torch" only)."""
     q = _rounder(emulate_f16, emulate)
     rg = _grad_rounder(emulate or ("fp16" if emulate_f16 else None), bwd_scale)
     x01 = (xyzs - (-scale)) / (2 * scale)
-    enc = rg(encode(x01, P.table, levels, impl))
+    enc0 = encode(x01, P.table, levels, impl)
+    if return_enc:
+        if enc0.requires_grad:
+            enc0.retain_grad()
+        else:
+            enc0.requires_grad_(True)
+    enc = rg(enc0)
     h = rg(q(torch.relu(rg(q(enc) @ q(P.W1).t()))) @ q(P.W2).t())
     sig = _TruncExp.apply(h[:, 0])
     d = dirs / torch.norm(dirs, dim=1, keepdim=True)
     g = torch.relu(rg(q(rgb_input(d, h)) @ q(P.W3).t()))
     g = torch.relu(rg(q(g) @ q(P.W4).t()))
     rgb = torch.sigmoid(rg(q(g) @ q(P.W5).t())[:, :3])
+    if return_enc:
+        return sig, rgb, h, enc0
     return sig, rgb, h
 
 

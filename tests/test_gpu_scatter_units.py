@@ -45,10 +45,25 @@ def test_scatter_matches_serial_oracle(dev, n, op, mode):
     1/S — exact, so the oracle scatters the unscaled values; "inf": one fp16 pair
     overflowed (GradScaler's skip case) — that level's maximum is inf, the scatter adds the level
     straight to the table with f32 atomics, and the inf / NaN (0 x inf) entries match the oracle's."""
+    scatter_case(dev, n, op, mode)
+
+
+def scatter_case(dev, n, op, mode, xw=None, with_order=False, inf_level=12):
+    """The body of test_scatter_matches_serial_oracle.  xw: the (n, 3) f32 world positions (default:
+    samples on rays inside the box); with_order: the stored gradient is in the processing order of
+    ncn_field_sort_windows on those positions and the scatter gathers the positions through it;
+    inf_level: the level of mode "inf"'s overflowed pair."""
     m = NGPMT(scale=0.5, grid_size=128).to(dev)
     levels = field_ref.grid_levels(0.5)[0]
-    xw = (_ray_samples(n, seed=n) - np.float32(0.5)).astype(np.float32)  # world positions
+    if xw is None:
+        xw = (_ray_samples(n, seed=n) - np.float32(0.5)).astype(np.float32)  # world positions
+    assert xw.shape == (n, 3) and xw.dtype == np.float32
     xyzs = torch.from_numpy(xw).to(dev)
+    order = None
+    if with_order:
+        order = torch.empty(n, dtype=torch.int32, device=dev)
+        assert _lib.lib().ncn_field_sort_windows(ptr(xyzs), I64(n), ptr(None), F32(m._xyz_min), F32(m._xyz_extent),
+                                                 ptr(order), stream()) == 0
     x01 = (xw + np.float32(0.5)).astype(np.float32)  # what the kernel forms: (x - xyz_min) * (1 / extent), extent 1
     rng = np.random.default_rng(n + 1)
     tdt = torch.float16 if op == "fp16" else torch.bfloat16
@@ -58,7 +73,7 @@ def test_scatter_matches_serial_oracle(dev, n, op, mode):
     gt_[torch.from_numpy(rng.random((n, 16)) < 0.2)] = 0  # zero contributions
     gt_[n // 3: n // 3 + 500] = 0  # a stretch of samples with nothing to add
     if mode == "inf":
-        gt_[n // 2, 12, 1] = float("inf")  # one overflowed pair on a fine level
+        gt_[n // 2, inf_level, 1] = float("inf")  # one overflowed pair (by default on a fine level)
     g = (gt_.float() / S).numpy()  # the unscaled operand-type values as f32 (exact: S is a power of two)
     # the dE workspace: header {1 / S, operand type (0 fp16, 1 bf16)}, then level-major [16][n_stride]
     # pairs of the operand type
@@ -75,17 +90,24 @@ def test_scatter_matches_serial_oracle(dev, n, op, mode):
     lmax[0] = torch.from_numpy(np.abs(g).max(axis=(0, 2)))  # (inf on the overflowed level, as the MLP pass records)
     lmax = lmax.to(dev)
     # oracle: serial f32 scatter of the same (fp16-valued) gradient
+    g_samples = g.reshape(n, 32)
+    if with_order:  # the pair stored at position p is sample order[p]'s
+        o = order.cpu().numpy().astype(np.int64)
+        assert np.array_equal(np.sort(o), np.arange(n))
+        g_samples = np.empty_like(g_samples)
+        g_samples[o] = g.reshape(n, 32)
     ref = field_ref._HashEncodeC.backward(
         type("Ctx", (), {"saved_tensors": (torch.from_numpy(x01),), "levels": levels,
                          "n_table": (m._n_table, 2)})(),
-        torch.from_numpy(np.ascontiguousarray(g.reshape(n, 32))))[1].numpy().astype(np.float64)
+        torch.from_numpy(np.ascontiguousarray(g_samples)))[1].numpy().astype(np.float64)
     # the positions in sample order (header flag 0: strided loads), then in the scatter's permuted
     # load order (ncn_field_scatter_positions, as the training step's MLP pass writes them)
-    for permuted in (False, True):
+    # (with an order the scatter gathers the positions through it and reads no permuted copy)
+    for permuted in ((False,) if with_order else (False, True)):
         if permuted:
             assert _lib.lib().ncn_field_scatter_positions(ptr(xyzs), I64(n), ptr(None), ptr(ws), stream()) == 0
         grad = torch.zeros(m._n_table, 2, dtype=torch.float32, device=dev)
-        rc = _lib.lib().ncn_field_scatter(ptr(xyzs), I64(n), ptr(None), ptr(None), m._levels_ptr, F32(m._xyz_min),
+        rc = _lib.lib().ncn_field_scatter(ptr(xyzs), I64(n), ptr(None), ptr(order), m._levels_ptr, F32(m._xyz_min),
                                           F32(m._xyz_extent), ptr(ws), ptr(lmax), I32(0), I32(16), I32(0), ptr(grad),
                                           stream())
         assert rc == 0, _lib.lib().ncn_last_error()

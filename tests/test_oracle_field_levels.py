@@ -1,0 +1,161 @@
+"""The per-level outlier criterion of the encoding gradient (tests/field_level_check.py), on the CPU:
+what the GPU test (tests/test_gpu_field_levels.py) holds the MLP pass's dE to.
+
+(a) The reference's own error stays inside the cap: the emulating oracle (operands rounded where
+    csrc/field.hip rounds them, forward and backward) run with fp32 tensors against the same run with
+    every tensor in fp64 — the same operand rounding points, only the accumulation differs (the
+    positions too: the encoding's weights then differ in their last bit, and most of the share comes
+    from operands that this flips; with fp32 positions it is 0.03 % / 0.02 %).  Every level's outlier
+    share <= 1 %.  Measured: worst level 0.35 % (fp16), 0.20 % (bf16); the GPU test's cap is 2 %.
+(b) The criterion rejects a systematic error: one level of the oracle's dE scaled by 1.01 (fp16) /
+    1.05 (bf16; its window 8 u = 3.1 % holds a 1 % scaling) has an outlier share above 50 %, on a
+    coarse, a middle and the finest level.
+(c) The oracle's weight gradients leave at most 2 of a matrix's 16-row tiles below the size at which
+    test_gpu_field.py::test_field_backward judges a tile, at that test's sizes and seeds.
+(d) The edge set of positions (field_level_check.place_edges) holds what it is meant to: x01 == 0
+    and 1, points whose floor is negative, the dense levels' wrapped boundary corner, and runs of
+    600 equal positions."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import field_ref
+from field_level_check import (MAX_SKIPPED_TILES, REPEAT, edge_points, outlier_share, place_edges,
+                               weight_tile_errors)
+
+N = 3000
+BWD_SCALE = {"fp16": 128.0, "bf16": 1.0}
+
+
+def _inputs(n, seed):  # (tests/test_gpu_field.py::_inputs)
+    g = torch.Generator().manual_seed(seed)
+    x = (torch.rand(n, 3, generator=g) - 0.5) * 0.999
+    d = torch.randn(n, 3, generator=g)
+    d = d / d.norm(dim=1, keepdim=True)
+    return x, d
+
+
+def _upstream(n):
+    g = torch.Generator().manual_seed(9)
+    return torch.randn(n, generator=g), torch.randn(n, 3, generator=g)
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle(precision, n, dtype, bwd_scale):
+    """(dL/denc (n, 32), the parameter gradients) of the emulating oracle with every tensor in dtype."""
+    P, levels = field_ref.init_params(seed=5, table_init=0.5)
+    x, d = _inputs(n, 2)
+    gs, gr = _upstream(n)
+    Pt = field_ref.FieldParams(*[t.to(dtype).requires_grad_(True) for t in P.tensors()])
+    sig, rgb, _, enc = field_ref.field_forward_autograd(x.to(dtype), d.to(dtype), Pt, levels, emulate=precision,
+                                                        bwd_scale=bwd_scale, return_enc=True)
+    assert enc.dtype == dtype and sig.dtype == dtype
+    ((sig * gs.to(dtype)).sum() + (rgb * gr.to(dtype)).sum()).backward()
+    return enc.grad.numpy().copy(), [t.grad.numpy().copy() for t in Pt.tensors()]
+
+
+def test_return_enc_keeps_outputs():
+    """return_enc adds the encoding and changes nothing else; its gradient is the table gradient's
+    source: scattering it (the serial C scatter) gives the table gradient autograd gives."""
+    P, levels = field_ref.init_params(seed=5, table_init=0.5)
+    x, d = _inputs(257, 2)
+    gs, gr = _upstream(257)
+    out = []
+    for ret in (False, True):
+        Pt = field_ref.FieldParams(*[t.clone().requires_grad_(True) for t in P.tensors()])
+        r = field_ref.field_forward_autograd(x, d, Pt, levels, emulate="fp16", bwd_scale=128.0, return_enc=ret)
+        assert len(r) == (4 if ret else 3)
+        ((r[0] * gs).sum() + (r[1] * gr).sum()).backward()
+        out.append((r, Pt))
+    (r0, P0), (r1, P1) = out
+    for a, b in zip(r0, r1[:3]):
+        assert torch.equal(a, b)
+    for a, b in zip(P0.tensors(), P1.tensors()):  # (autograd's index scatter sums in no fixed order)
+        assert float((a.grad - b.grad).norm() / b.grad.norm()) < 1e-6
+    enc = r1[3]
+    assert enc.shape == (257, 32) and enc.grad is not None and enc.grad.shape == (257, 32)
+    ctx = type("Ctx", (), {"saved_tensors": ((x + 0.5),), "levels": levels, "n_table": tuple(P.table.shape)})()
+    dt = field_ref._HashEncodeC.backward(ctx, enc.grad)[1]
+    rel = float((dt - P1.table.grad).norm() / P1.table.grad.norm())
+    assert rel < 1e-5, rel
+
+
+@pytest.mark.parametrize("precision", ["fp16", "bf16"])
+def test_reference_accumulation_inside_cap(precision):
+    de32, _ = _oracle(precision, N, torch.float32, BWD_SCALE[precision])
+    de64, _ = _oracle(precision, N, torch.float64, BWD_SCALE[precision])
+    share = outlier_share(de32, de64, precision)
+    print(f"{precision}: fp32 vs fp64 accumulation, dE outlier share per level (%):",
+          " ".join(f"{100 * s:.2f}" for s in share))
+    assert share.max() <= 0.01, share
+
+
+@pytest.mark.parametrize("level", [1, 8, 15])
+@pytest.mark.parametrize("precision", ["fp16", "bf16"])
+def test_criterion_rejects_scaled_level(precision, level):
+    ref, _ = _oracle(precision, N, torch.float32, BWD_SCALE[precision])
+    got = ref.copy()
+    got[:, 2 * level:2 * level + 2] *= 1.01 if precision == "fp16" else 1.05
+    share = outlier_share(got, ref, precision)
+    print(f"{precision}: level {level} scaled, outlier share {100 * share[level]:.1f} %")
+    assert share[level] > 0.5, share
+    others = np.delete(share, level)
+    assert others.max() == 0.0  # (the other levels are untouched)
+
+
+@pytest.mark.parametrize("precision", ["fp16", "bf16"])
+@pytest.mark.parametrize("n", [3000, 4097, 12289])  # (test_field_backward's sizes)
+def test_oracle_weight_tiles_are_judged(precision, n):
+    """test_field_backward's reference (no backward rounding): at most MAX_SKIPPED_TILES tiles per
+    matrix fall below the size at which a tile is judged."""
+    _, grads = _oracle(precision, n, torch.float32, None)
+    for name, g in zip(("W1", "W2", "W3", "W4", "W5"), grads[1:]):
+        errs, skipped = weight_tile_errors(g, g)
+        assert len(skipped) <= MAX_SKIPPED_TILES, (name, skipped)
+        assert all(e == 0.0 for e in errs.values())
+        assert len(errs) >= 1
+
+
+def test_edge_set_reaches_the_edges():
+    levels = field_ref.grid_levels(0.5)[0]
+    spec, rep_in, rep_face = edge_points(levels)
+    x01 = spec + np.float32(0.5)
+    assert (x01 == 0).any() and (x01 == 1).any()
+    assert (np.abs(spec) == 0.5).all(axis=1).sum() == 8  # the corners
+    assert (x01 < 0).all(axis=1).any() and (x01 > 1).all(axis=1).any()
+    # a negative floor on every level: (uint32)(int)floor = 0xFFFFFFFF.. (beyond the cell key range)
+    for lv in levels:
+        pos = np.float32(lv["scale"]) * x01 + np.float32(0.5)
+        assert (np.floor(pos) < 0).any()
+    # the dense levels' boundary corner, index >= params before the modulo: inside the box only where
+    # the level's scale is an integer (level 0: x01 == 1 gives the corner coordinate res), on every
+    # dense level for the points 0.1 outside on the high side of all three axes
+    def top_corner(lv, v01):
+        p = int(np.floor(np.float32(lv["scale"]) * np.float32(v01) + np.float32(0.5))) + 1
+        return p + lv["res"] * p + lv["res"] ** 2 * p
+    assert top_corner(levels[0], 1.0) >= levels[0]["params"]
+    assert (x01 == np.float32(0.7) + np.float32(0.5)).any(axis=1).any()
+    for lv in levels[:6]:
+        assert not lv["hashed"]
+        assert top_corner(lv, np.float32(0.7) + np.float32(0.5)) >= lv["params"]
+    assert all(lv["hashed"] for lv in levels[6:])
+    # the cell-boundary pairs fall into neighbouring cells of their level
+    for l in (0, 5, 10):
+        pos = np.float32(levels[l]["scale"]) * x01[:, 0] + np.float32(0.5)
+        fl = np.floor(pos)
+        assert ((np.abs(pos - np.round(pos)) < 1e-3) & (fl >= 1)).sum() >= 6
+    for n in (4099, 2 * 4096 + 5):
+        fill = np.zeros((n, 3), np.float32)
+        x, mark = place_edges(fill, levels)
+        assert mark[0] and mark[4095] and mark[4096] and mark[n - 1]
+        assert (x[~mark] == 0).all()
+        k = len(spec)
+        assert np.array_equal(x[:k], spec) and (x[k:k + REPEAT] == rep_in).all()
+        assert (x[k + REPEAT:k + 2 * REPEAT] == rep_face).all() and rep_face[0] == -0.5
+        # special points on both sides of index 4096
+        is_spec = lambda i: any(np.array_equal(x[i], s) for s in spec)  # noqa: E731
+        assert is_spec(4095) and is_spec(4096)
+        if n > 8192:
+            assert np.array_equal(x[n - k:], spec)
