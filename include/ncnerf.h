@@ -91,7 +91,10 @@ int ncn_march_train_pack(const float* rays_d, const int64_t* rays_a, int64_t n_r
  *   dL_drays_o[r] = sum_{s in [indptr[r], indptr[r+1])} dL_dxyzs[s]              (n_rays, 3)
  *   dL_drays_d[r] = sum_{s in [indptr[r], indptr[r+1])} dL_dxyzs[s] * ts[s] + dL_ddirs[s]
  * One wave per row, fixed summation order (no atomics): deterministic run to run.  dL_dxyzs or
- * dL_ddirs may be NULL (a zero gradient). */
+ * dL_ddirs may be NULL (a zero gradient).
+ * PRECONDITION: every indptr entry (each rays_a[r,1], and rays_a[-1,1] + rays_a[-1,2]) lies in
+ * [0, S], S the row count of dL_dxyzs / dL_ddirs / ts (the marcher's total): the kernel reads
+ * those rows unclamped, so the caller checks the bounds (vren.raymarching_train_backward does). */
 int ncn_segment_csr(const float* dL_dxyzs, const float* dL_ddirs, const float* ts, const int64_t* rays_a,
                     int64_t n_rays, float* dL_drays_o, float* dL_drays_d, void* stream);
 
@@ -288,6 +291,34 @@ int ncn_field_bwd_mlp(const float* xyzs, const float* dirs, int64_t n, const int
                       const uint16_t* weights_packed,
                       int precision, const uint16_t* enc_cache, const float* dL_dsigmas, const float* dL_drgbs,
                       const float* loss_scale, float* slab, float* dE_ws, float* level_max, void* stream);
+/* ---- input gradients of the field (camera pose refinement, train_nerf.py --optimize_ext: the rays
+ *      require grad, and RayMarcher.backward / ncn_segment_csr folds dL/dxyzs and dL/ddirs into them;
+ *      also d sigma / d x of NGPMT.density, the analytic normal).  Neither kernel uses atomics: two
+ *      runs are bit-identical.  Both outputs are (n, 3) fp32 in SAMPLE order whatever `order` is,
+ *      and rows [*n_dev, n) are written as zeros (the caller need not clear them). ---- */
+/* ncn_field_bwd_mlp that also writes dL_ddirs.  g_in[k] = sum_j W3[j,k] dD3[j] (k = 0..2: the
+ * direction columns of w_master's W3, the NCN_FIELD_NW fp32 masters, rounded to the operand type;
+ * dD3 the layer-3 pre-activation gradient in the operand type at the chain's scale S; fp32
+ * accumulation), rounded to the operand type at that scale as the encoding gradient is (tcnn hands
+ * dL/dinput on in network precision), divided by S, then the normalisation's backward in fp32:
+ * dL/dd = (g_in - n (n . g_in)) / |d|, n = d / |d|.  slab, dE_ws and level_max are bit for bit
+ * ncn_field_bwd_mlp's.  dirs NULL (density mode) is an error.  Under the internal fp16 GradScaler
+ * an overflowed chain leaves non-finite rows: the caller skips that step as the optimizer does. */
+int ncn_field_bwd_mlp_din(const float* xyzs, const float* dirs, int64_t n, const int32_t* n_dev, const int32_t* order,
+                          const uint16_t* weights_packed, int precision, const uint16_t* enc_cache,
+                          const float* dL_dsigmas, const float* dL_drgbs, const float* loss_scale, float* slab,
+                          float* dE_ws, float* level_max, const float* w_master, float* dL_ddirs, void* stream);
+/* dL/dx from the dE workspace an MLP pass left (ncn_field_bwd_mlp / _mlp_din / _mlp_part's sigma
+ * part; it only reads the header {1 / S, operand type} and the level-major encoding gradient, in
+ * processing order, so it may run before, after or beside the table scatter):
+ *   dL/dx_k = (1 / xyz_extent) (1 / S) sum_l scale_l sum_f dE[l,f] sum_{4 corners of the other two
+ *             dims} w_other (table[hi_k]_f - table[lo_k]_f)
+ * — the derivative of tcnn's linear interpolation, piecewise constant along k, with the cell, wrap
+ * and index of ncn_field_fwd (fp32 fmaf(scale, x01, 0.5), floorf).  fp16 dE is at the chain's scale
+ * S (divided out here), bf16 dE is unscaled; non-finite dE propagates to the row, unmasked. */
+int ncn_field_bwd_dx(const float* xyzs, int64_t n, const int32_t* n_dev, const int32_t* order, const float* table,
+                     const uint32_t* levels, float xyz_min, float xyz_extent, const float* dE_ws, float* dL_dxyzs,
+                     void* stream);
 /* The MLP pass split by the gradient's source (the fused training step runs the rgb part while
  * the normal clustering computes the depth gradient): part 1 (rgb) = the rgb_net path from
  * dL_drgbs alone — slab tiles of W3..W5 (rows [0, its grid)) and the rgb part of dL/dh into
@@ -357,6 +388,14 @@ int ncn_normals_fwd(const float* rays_o, const float* rays_d, const float* depth
 int ncn_normals_bwd(const float* rays_o, const float* rays_d, const float* depth, const int64_t* x1,
                     const int64_t* x2, const int64_t* x3, int64_t n_tri, const float* dL_dnormals,
                     const float* term_weights, float* dL_ddepth, void* stream);
+/* ncn_normals_bwd that also accumulates (+=, f32 atomics over the triangle corners) the gradients
+ * of the rays through P = rays_o + rays_d * depth: dL_drays_o, dL_drays_d (n_rays, 3), zeroed by
+ * the caller.  rays_o and rays_d may be the same array (render()'s quirk q1); the two outputs stay
+ * separate. */
+int ncn_normals_bwd_rays(const float* rays_o, const float* rays_d, const float* depth, const int64_t* x1,
+                         const int64_t* x2, const int64_t* x3, int64_t n_tri, const float* dL_dnormals,
+                         const float* term_weights, float* dL_ddepth, float* dL_drays_o, float* dL_drays_d,
+                         void* stream);
 /* Photometric MSE + weighted opacity entropy (losses.py:349-362) with the validity filter
  * (losses.py:246-262): loss[0] = mean((rgb-gt)^2), loss[1] = w_opacity*mean(-o log o), o = opacity+1e-10,
  * loss[2..3] = 1 if the term is finite (else the term and its gradient are 0).  The backward

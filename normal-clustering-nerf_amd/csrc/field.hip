@@ -615,11 +615,19 @@ __device__ __forceinline__ float lmax_upd(float m, float a, float b) {  // non-f
 template <int PART> constexpr int x_count() { return PART == BWD_SIGMA ? N_XFRAG - XA2 : N_XFRAG; }
 template <int PART> constexpr int x_origin() { return PART == BWD_SIGMA ? XA2 : 0; }
 
-template <typename T, int PART, typename FR>
+// (DIN, the one-pass form only) the direction gradient's operands: W3's three direction columns
+// rounded to T in LDS ([k][64 rows]), the processing order and the output (n, 3) in sample order
+template <typename T>
+struct DinCtx {
+    const T* w3d;
+    const int32_t* order;
+    float* out;
+};
+template <typename T, int PART, bool DIN = false, typename FR>
 __device__ __forceinline__ void bwd_group(const FR& F, uint16_t* Xw, const BwdIn<T>& cur, int64_t grp,
                                           int64_t n, int64_t n_stride, int lane, float* __restrict__ dE_out,
                                           float (&lm)[4], float inv_S, typename Mfma<T>::v4* __restrict__ stq,
-                                          float* __restrict__ sth0) {
+                                          float* __restrict__ sth0, const DinCtx<T>* din = nullptr) {
     typedef Mfma<T> M;
     typedef typename M::v4 v4;
     typedef typename M::v8 v8;
@@ -668,6 +676,37 @@ __device__ __forceinline__ void bwd_group(const FR& F, uint16_t* Xw, const BwdIn
     for (int t = 0; t < 4; t++) x_put(Xw + (XA3 + t) * 256, lane, dD3[t]);
     x_put(Xw + XB3D * 256, lane, st.x3d);
     x_put(Xw + XB3H * 256, lane, st.x3h);
+    if constexpr (DIN) {
+        // dL/d(d/|d|) = W3[:, 0:3]^T dD3: the lane's 16 rows (tile t rows 4g..4g+3) against the
+        // rounded columns in fp32, then the four row groups summed by two fixed exchanges (every
+        // lane forms the same sum).  Handed on in the operand type at the chain's scale, as tcnn
+        // hands a network's input gradient on, then unscaled; the normalisation's backward in fp32.
+        float gi[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                const v4 w = *(const v4*)(din->w3d + k * 64 + 16 * t + 4 * g);
+#pragma unroll
+                for (int i = 0; i < 4; i++) gi[k] = fmaf((float)w[i], (float)dD3[t][i], gi[k]);
+            }
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            gi[k] += __shfl_xor(gi[k], 16);
+            gi[k] += __shfl_xor(gi[k], 32);
+        }
+        if (g == 0 && valid) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) gi[k] = (float)(T)gi[k] * inv_S;
+            const float nrm = sqrtf(cur.dx * cur.dx + cur.dy * cur.dy + cur.dz * cur.dz);
+            const float nx = cur.dx / nrm, ny = cur.dy / nrm, nz = cur.dz / nrm;
+            const float ng = nx * gi[0] + ny * gi[1] + nz * gi[2];
+            float* o = din->out + 3 * (din->order ? (int64_t)din->order[s] : s);
+            o[0] = (gi[0] - nx * ng) / nrm;
+            o[1] = (gi[1] - ny * ng) / nrm;
+            o[2] = (gi[2] - nz * ng) / nrm;
+        }
+    }
     // L3 backward -> dh (rgb path) ; + TruncExp backward on h[0]
     dh = M::k32(F.a32(B_L3, lane), cat8<v8>(dD3[0], dD3[1]), zero4());
     dh = M::k32(F.a32(B_L3 + 1, lane), cat8<v8>(dD3[2], dD3[3]), dh);
@@ -884,14 +923,16 @@ __host__ __device__ inline int bwd_blocks_of(int64_t n) {
     return (int)(b < 1 ? 1 : (b > 256 ? 256 : b));
 }
 
-template <typename T, int PART = BWD_ALL>
+template <typename T, int PART = BWD_ALL, bool DIN = false>
 __global__ __launch_bounds__(BWD_THREADS) void field_bwd_kernel(
     const float* __restrict__ dirs, int64_t n, const int32_t* __restrict__ n_dev, const uint16_t* __restrict__ wpacked,
     const typename Mfma<T>::v8* __restrict__ enc_cache, const float* __restrict__ dL_dsig,
     const float* __restrict__ dL_drgb, const float* __restrict__ loss_scale, float* __restrict__ dE_out,
     float* __restrict__ slab, float* __restrict__ level_max, const int32_t* __restrict__ order,
     const float* __restrict__ dL_dsig2 = nullptr, float* __restrict__ stash = nullptr,
-    const float* __restrict__ xyzs = nullptr) {
+    const float* __restrict__ xyzs = nullptr, const float* __restrict__ w_master = nullptr,
+    float* __restrict__ dL_ddirs = nullptr) {
+    static_assert(!DIN || PART == BWD_ALL, "the direction gradient leaves the one-pass form only");
     typedef typename Mfma<T>::v4 v4;
     // AMP loss scale (GradScaler of the reference's precision=16 run) times tcnn's fp16 module loss
     // scale (128): the fp16 chain sees the upstream gradients times S (a power of two), dE and dW
@@ -921,6 +962,7 @@ __global__ __launch_bounds__(BWD_THREADS) void field_bwd_kernel(
     // fp32 row-0 elements (capacity groups: the layout does not depend on the device count)
     v4* stq = (v4*)stash;
     float* sth0 = stash ? stash + ((n + 15) / 16) * 128 : nullptr;
+    const int64_t n_cap = n;
     if (n_dev) n = min<int64_t>(n, *n_dev);
     // the sigma pass keeps only the sigma_net fragments and its 11 exchange tiles per group (57 KB:
     // two workgroups per CU); the others all 34 + 8 fragments and 30 tiles (158 KB)
@@ -941,6 +983,16 @@ __global__ __launch_bounds__(BWD_THREADS) void field_bwd_kernel(
     if constexpr (PART == BWD_RGB) {  // the sigma pass max-reduces into the level_max rows: zero them
         if (blockIdx.x == 0 && level_max)
             for (int i = threadIdx.x; i < lm_rows * 16; i += BWD_THREADS) level_max[i] = 0.f;
+    }
+    DinCtx<T> din = {nullptr, order, dL_ddirs};
+    if constexpr (DIN) {
+        __shared__ __attribute__((aligned(16))) T W3d[3 * 64];  // W3[j][k] of the fp32 masters at [k][j]
+        for (int i = threadIdx.x; i < 3 * 64; i += BWD_THREADS) W3d[i] = (T)w_master[W3_OFF + (i & 63) * 32 + (i >> 6)];
+        din.w3d = W3d;
+        // the rows past the device count leave as zeros
+        for (int64_t i = 3 * n + (int64_t)blockIdx.x * BWD_THREADS + threadIdx.x; i < 3 * n_cap;
+             i += (int64_t)gridDim.x * BWD_THREADS)
+            dL_ddirs[i] = 0.f;
     }
     __syncthreads();
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -972,10 +1024,18 @@ __global__ __launch_bounds__(BWD_THREADS) void field_bwd_kernel(
             const int z = opaque_zero();
             F.f32 = F32s + z;
             F.f16 = F16s + z;
-            bwd_group<T, PART>(F, X + wid * NX * 256, cur, grp, n, n_stride, lane, dE_pairs, lm, inv_S, stq, sth0);
+            bwd_group<T, PART, DIN>(F, X + wid * NX * 256, cur, grp, n, n_stride, lane, dE_pairs, lm, inv_S, stq, sth0,
+                                    &din);
         }
         lds_barrier();  // (the dE stores and the next step's loads stay in flight)
-        bwd_dw<T, PART>(X, ng, wid, lane, acc);
+        if constexpr (DIN) {
+            // The transposed LDS reads of phase 2 must run with EXEC all ones (x_get): the group count
+            // and the wave index are uniform, but this instantiation's register allocation keeps them
+            // in vector registers, and a zero half of x_pair then becomes a read under EXEC = 0, which
+            // returns the stale tile.  As scalars they are branches again.
+            bwd_dw<T, PART>(X, __builtin_amdgcn_readfirstlane(ng), __builtin_amdgcn_readfirstlane(wid), lane, acc);
+        } else
+            bwd_dw<T, PART>(X, ng, wid, lane, acc);
         lds_barrier();
     }
     bwd_store_dw<PART>(slab + (int64_t)blockIdx.x * NCN_FIELD_NW, wid, lane, acc, inv_S);
@@ -2033,6 +2093,111 @@ __global__ __launch_bounds__(SC_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
 #endif
 }
 
+// ---------------------------------------------------------------------------------------------
+// Encoding input gradient dL/dx (ncn_field_bwd_dx): the derivative of the trilinear interpolation
+// contracted with the encoding gradient the MLP pass left in the dE workspace.  Along dimension k
+// the interpolation is linear inside a cell, so per level and feature
+//   d enc / d x01_k = scale * sum over the 4 corner pairs of the other two dims of
+//                     w_other * (T[hi_k] - T[lo_k]),
+// piecewise constant along k, with the forward's cell choice (level_pos: the same fmaf / floorf).
+// Same shape as the forward: lane (g, r) of a wave takes levels {2g, 2g+1, 8+2g, 9+2g} of the
+// sample at processing position r of its group (its dE pairs are the 64 contiguous bytes a row of
+// 16 lanes reads per level), two levels' gathers in flight, fp32 accumulation in a fixed order,
+// the four row groups summed by two fixed exchanges, one 12-byte store per sample (sample order).
+// No atomics: two runs are bit-identical.  Non-finite dE (an overflowed fp16 chain) propagates.
+__device__ __forceinline__ float de_value(uint32_t bits16, bool bf16) {
+    return bf16 ? __uint_as_float(bits16 << 16) : (float)__builtin_bit_cast(_Float16, (uint16_t)bits16);
+}
+__device__ __forceinline__ void dx_level(const float2* __restrict__ tab, const LevelTable& L, int l, float x, float y,
+                                         float z, uint32_t dE, bool bf16, float (&acc)[3]) {
+    const LevelPos p = level_pos(L.scale[l], x, y, z);
+    ScLevel sl;
+    sl.res = L.res[l]; sl.params = L.params[l];
+    sl.dense = (uint64_t)sl.res * sl.res * sl.res <= sl.params;
+    uint32_t e[8];
+    sc_corner_entries(sl, p.px, p.py, p.pz, e);
+    const uint32_t off = L.offset[l];
+    float2 v[8];
+#pragma unroll
+    for (int c = 0; c < 8; c++) v[c] = tab[off + e[c]];
+    const float d0 = de_value(dE & 0xFFFFu, bf16), d1 = de_value(dE >> 16, bf16);
+    float u[8];  // the corner values contracted with the level's two dE features
+#pragma unroll
+    for (int c = 0; c < 8; c++) u[c] = fmaf(d1, v[c].y, d0 * v[c].x);
+    const float wx[2] = {1.0f - p.fx, p.fx}, wy[2] = {1.0f - p.fy, p.fy}, wz[2] = {1.0f - p.fz, p.fz};
+    float gx = 0.f, gy = 0.f, gz = 0.f;
+#pragma unroll
+    for (int b = 0; b < 2; b++)
+#pragma unroll
+        for (int a = 0; a < 2; a++) {
+            gx = fmaf(wy[a] * wz[b], u[1 + 2 * a + 4 * b] - u[2 * a + 4 * b], gx);
+            gy = fmaf(wx[a] * wz[b], u[a + 2 + 4 * b] - u[a + 4 * b], gy);
+            gz = fmaf(wx[a] * wy[b], u[a + 2 * b + 4] - u[a + 2 * b], gz);
+        }
+    acc[0] = fmaf(L.scale[l], gx, acc[0]);
+    acc[1] = fmaf(L.scale[l], gy, acc[1]);
+    acc[2] = fmaf(L.scale[l], gz, acc[2]);
+}
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void field_bwd_dx_kernel(
+    const float* __restrict__ xyzs, int64_t n_cap, const int32_t* __restrict__ n_dev, const int32_t* __restrict__ order,
+    const float2* __restrict__ table, LevelTable Lt, float xyz_min, float xyz_extent, const float* __restrict__ dE_ws,
+    float* __restrict__ dL_dxyzs) {
+    __shared__ LevelTable L;
+    load_levels(L, Lt);
+    __syncthreads();
+    const int64_t n = n_dev ? min<int64_t>(n_cap, *n_dev) : n_cap;
+    const int64_t n_stride = (n_cap + 3) & ~(int64_t)3;  // dE layout [16][n_stride] pairs behind the header
+    const float out_scale = dE_ws[0] / xyz_extent;         // 1 / S (the chain's scale) and d x01 / d x
+    const bool bf16 = dE_ws[1] != 0.f;
+    const uint32_t* __restrict__ dE = (const uint32_t*)(dE_ws + DE_HEADER_FLOATS);
+    const int lane = threadIdx.x & 63, g = lane >> 4, r = lane & 15;
+    const int64_t n_groups = (n_cap + 15) / 16;
+    const int64_t wave0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * 4;
+    for (int64_t grp = wave0; grp < n_groups; grp += n_waves) {
+        const int64_t pos = grp * 16 + r;
+        if (grp * 16 >= n) {  // (uniform) rows past the device count leave as zeros
+            if (g < 3 && pos < n_cap) dL_dxyzs[3 * pos + g] = 0.f;
+            continue;
+        }
+        const bool valid = pos < n;
+        const int64_t s = valid && order ? (int64_t)order[pos] : pos;
+        float x = 0.f, y = 0.f, z = 0.f;
+        uint32_t q[4] = {0u, 0u, 0u, 0u};
+        if (valid) {
+            x = (xyzs[3 * s] - xyz_min) / xyz_extent;
+            y = (xyzs[3 * s + 1] - xyz_min) / xyz_extent;
+            z = (xyzs[3 * s + 2] - xyz_min) / xyz_extent;
+            q[0] = dE[(int64_t)(2 * g) * n_stride + pos];
+            q[1] = dE[(int64_t)(2 * g + 1) * n_stride + pos];
+            q[2] = dE[(int64_t)(8 + 2 * g) * n_stride + pos];
+            q[3] = dE[(int64_t)(9 + 2 * g) * n_stride + pos];
+        }
+        float acc[3] = {0.f, 0.f, 0.f};
+        dx_level(table, L, 2 * g, x, y, z, q[0], bf16, acc);
+        dx_level(table, L, 2 * g + 1, x, y, z, q[1], bf16, acc);
+        // (as the forward: the last two levels' gathers wait for the first two's results)
+        asm volatile("; dx: levels 8+ after 0-7 %1 %2" : "+v"(x) : "v"(acc[0]), "v"(acc[1]));
+        dx_level(table, L, 8 + 2 * g, x, y, z, q[2], bf16, acc);
+        dx_level(table, L, 9 + 2 * g, x, y, z, q[3], bf16, acc);
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            acc[k] += __shfl_xor(acc[k], 16);
+            acc[k] += __shfl_xor(acc[k], 32);
+        }
+        if (pos < n_cap) {  // (a partial last group: its rows past the count are zero too)
+            if (g == 0 && valid) {
+                dL_dxyzs[3 * s] = acc[0] * out_scale;
+                dL_dxyzs[3 * s + 1] = acc[1] * out_scale;
+                dL_dxyzs[3 * s + 2] = acc[2] * out_scale;
+            } else if (g == 0) {
+                dL_dxyzs[3 * pos] = 0.f; dL_dxyzs[3 * pos + 1] = 0.f; dL_dxyzs[3 * pos + 2] = 0.f;
+            }
+        }
+    }
+}
+
 static int scatter_grid(int64_t n_cap) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(256 * 1024 / SC_THREADS, (n_cap + 255) / 256));  // 1024 threads per CU
 }
@@ -2173,6 +2338,51 @@ int ncn_field_bwd_mlp(const float* xyzs, const float* dirs, int64_t n, const int
                              weights_packed, enc_cache, dL_dsigmas, dL_drgbs, loss_scale, dE_ws, slab, level_max, order,
                              nullptr, nullptr);
     NCN_LAUNCH_CHECK("ncn_field_bwd_mlp");
+    return 0;
+}
+
+int ncn_field_bwd_mlp_din(const float* xyzs, const float* dirs, int64_t n, const int32_t* n_dev, const int32_t* order,
+                          const uint16_t* weights_packed, int precision, const uint16_t* enc_cache,
+                          const float* dL_dsigmas, const float* dL_drgbs, const float* loss_scale, float* slab,
+                          float* dE_ws, float* level_max, const float* w_master, float* dL_ddirs, void* stream) {
+    if (n <= 0) return 0;
+    NCN_REQUIRE(precision == NCN_PREC_F16 || precision == NCN_PREC_BF16, hipErrorInvalidValue,
+                "ncn_field_bwd_mlp_din: precision must be NCN_PREC_F16 or NCN_PREC_BF16");
+    NCN_REQUIRE(dirs != nullptr, hipErrorInvalidValue,
+                "ncn_field_bwd_mlp_din: no direction gradient without dirs (density mode)");
+    NCN_REQUIRE(w_master != nullptr && dL_ddirs != nullptr, hipErrorInvalidValue,
+                "ncn_field_bwd_mlp_din: w_master and dL_ddirs required");
+    NCN_REQUIRE(((uintptr_t)dE_ws & 15) == 0 && ((uintptr_t)enc_cache & 15) == 0 && ((uintptr_t)weights_packed & 15) == 0,
+                hipErrorInvalidValue, "ncn_field_bwd_mlp_din: dE_ws / enc_cache / weights_packed must be 16-byte aligned");
+    NCN_REQUIRE(level_max != nullptr, hipErrorInvalidValue, "ncn_field_bwd_mlp_din: level_max workspace required");
+    NCN_REQUIRE(((uintptr_t)xyzs & 15) == 0, hipErrorInvalidValue, "ncn_field_bwd_mlp_din: xyzs must be 16-byte aligned");
+    const int nb = ncn_field_bwd_blocks(n);
+    const hipStream_t st = (hipStream_t)stream;
+    if (precision == NCN_PREC_F16)
+        hipLaunchKernelGGL((field_bwd_kernel<_Float16, BWD_ALL, true>), dim3(nb), dim3(BWD_THREADS), 0, st, dirs, n, n_dev,
+                           weights_packed, (const Mfma<_Float16>::v8*)enc_cache, dL_dsigmas, dL_drgbs, loss_scale, dE_ws,
+                           slab, level_max, order, (const float*)nullptr, (float*)nullptr, xyzs, w_master, dL_ddirs);
+    else
+        hipLaunchKernelGGL((field_bwd_kernel<__bf16, BWD_ALL, true>), dim3(nb), dim3(BWD_THREADS), 0, st, dirs, n, n_dev,
+                           weights_packed, (const Mfma<__bf16>::v8*)enc_cache, dL_dsigmas, dL_drgbs, loss_scale, dE_ws,
+                           slab, level_max, order, (const float*)nullptr, (float*)nullptr, xyzs, w_master, dL_ddirs);
+    NCN_LAUNCH_CHECK("ncn_field_bwd_mlp_din");
+    return 0;
+}
+
+int ncn_field_bwd_dx(const float* xyzs, int64_t n, const int32_t* n_dev, const int32_t* order, const float* table,
+                     const uint32_t* levels, float xyz_min, float xyz_extent, const float* dE_ws, float* dL_dxyzs,
+                     void* stream) {
+    if (n <= 0) return 0;
+    NCN_REQUIRE(xyzs && table && levels && dE_ws && dL_dxyzs, hipErrorInvalidValue,
+                "ncn_field_bwd_dx: xyzs, table, levels, dE_ws and dL_dxyzs required");
+    NCN_REQUIRE(xyz_extent > 0.f, hipErrorInvalidValue, "ncn_field_bwd_dx: xyz_extent must be positive");
+    NCN_REQUIRE(((uintptr_t)table & 7) == 0 && ((uintptr_t)dE_ws & 15) == 0, hipErrorInvalidValue,
+                "ncn_field_bwd_dx: table 8-byte, dE_ws 16-byte aligned");
+    const LevelTable Lt = make_table(levels);
+    hipLaunchKernelGGL(field_bwd_dx_kernel, dim3(fwd_grid(n)), dim3(256), 0, (hipStream_t)stream, xyzs, n, n_dev, order,
+                       (const float2*)table, Lt, xyz_min, xyz_extent, dE_ws, dL_dxyzs);
+    NCN_LAUNCH_CHECK("ncn_field_bwd_dx");
     return 0;
 }
 

@@ -107,6 +107,55 @@ __global__ void normals_bwd_kernel(const float* __restrict__ o, const float* __r
     atomicAdd(ddepth + i3, g3);
 }
 
+// The same backward with the rays' gradients (camera pose refinement: rays_o / rays_d require
+// grad): dL/dP1 = -(da + db), dL/dP2 = da, dL/dP3 = db through P = o + d * depth, so per corner
+// dL/do += dL/dP, dL/dd += depth * dL/dP, dL/ddepth += d . dL/dP (the sums of ncn_normals_bwd).
+__global__ void normals_bwd_rays_kernel(const float* __restrict__ o, const float* __restrict__ d,
+                                        const float* __restrict__ depth, const int64_t* __restrict__ x1,
+                                        const int64_t* __restrict__ x2, const int64_t* __restrict__ x3, int64_t T,
+                                        const float* __restrict__ dn, const float* __restrict__ tw,
+                                        float* __restrict__ ddepth, float* __restrict__ d_o, float* __restrict__ d_d) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= T) return;
+    const int64_t idx[3] = {x1[t], x2[t], x3[t]};
+    float g[3];
+    tri_normal_grad(dn, tw, T, t, g);
+    float P1[3], P2[3], P3[3];
+    tri_points(o, d, depth, idx[0], P1);
+    tri_points(o, d, depth, idx[1], P2);
+    tri_points(o, d, depth, idx[2], P3);
+    const float a[3] = {P2[0] - P1[0], P2[1] - P1[1], P2[2] - P1[2]};
+    const float b[3] = {P3[0] - P1[0], P3[1] - P1[1], P3[2] - P1[2]};
+    const float c[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+    const float len = sqrtf(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+    float dc[3];
+    if (len > 1e-12f) {
+        const float n[3] = {c[0] / len, c[1] / len, c[2] / len};
+        const float ng = n[0] * g[0] + n[1] * g[1] + n[2] * g[2];
+#pragma unroll
+        for (int k = 0; k < 3; k++) dc[k] = (g[k] - n[k] * ng) / len;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; k++) dc[k] = g[k] / 1e-12f;
+    }
+    const float da[3] = {b[1] * dc[2] - b[2] * dc[1], b[2] * dc[0] - b[0] * dc[2], b[0] * dc[1] - b[1] * dc[0]};
+    const float db[3] = {dc[1] * a[2] - dc[2] * a[1], dc[2] * a[0] - dc[0] * a[2], dc[0] * a[1] - dc[1] * a[0]};
+    const float dP[3][3] = {{-(da[0] + db[0]), -(da[1] + db[1]), -(da[2] + db[2])},
+                            {da[0], da[1], da[2]},
+                            {db[0], db[1], db[2]}};
+#pragma unroll
+    for (int v = 0; v < 3; v++) {
+        const int64_t i = idx[v];
+        const float dep = depth[i];
+        atomicAdd(ddepth + i, dP[v][0] * d[3 * i] + dP[v][1] * d[3 * i + 1] + dP[v][2] * d[3 * i + 2]);
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            atomicAdd(d_o + 3 * i + k, dP[v][k]);
+            atomicAdd(d_d + 3 * i + k, dP[v][k] * dep);
+        }
+    }
+}
+
 // ---- photometric MSE + opacity entropy (losses.py:349-362, validity filter :246-262) ----
 // One workgroup: loss[0] = mean((rgb - gt)^2), loss[1] = w_op * mean(-o log o), o = opacity + 1e-10.
 constexpr int PH_THREADS = 1024;
@@ -1204,6 +1253,19 @@ int ncn_normals_bwd(const float* rays_o, const float* rays_d, const float* depth
     hipLaunchKernelGGL(normals_bwd_kernel, dim3(cdiv(n_tri, 256)), dim3(256), 0, (hipStream_t)stream, rays_o, rays_d,
                        depth, x1, x2, x3, n_tri, dL_dnormals, term_weights, dL_ddepth);
     NCN_LAUNCH_CHECK("ncn_normals_bwd");
+    return 0;
+}
+
+int ncn_normals_bwd_rays(const float* rays_o, const float* rays_d, const float* depth, const int64_t* x1,
+                         const int64_t* x2, const int64_t* x3, int64_t n_tri, const float* dL_dnormals,
+                         const float* term_weights, float* dL_ddepth, float* dL_drays_o, float* dL_drays_d,
+                         void* stream) {
+    if (n_tri <= 0) return 0;
+    NCN_REQUIRE(dL_ddepth && dL_drays_o && dL_drays_d, hipErrorInvalidValue,
+                "ncn_normals_bwd_rays: dL_ddepth, dL_drays_o and dL_drays_d required");
+    hipLaunchKernelGGL(normals_bwd_rays_kernel, dim3(cdiv(n_tri, 256)), dim3(256), 0, (hipStream_t)stream, rays_o,
+                       rays_d, depth, x1, x2, x3, n_tri, dL_dnormals, term_weights, dL_ddepth, dL_drays_o, dL_drays_d);
+    NCN_LAUNCH_CHECK("ncn_normals_bwd_rays");
     return 0;
 }
 

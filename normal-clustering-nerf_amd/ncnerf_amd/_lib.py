@@ -59,6 +59,8 @@ SIGNATURES = {
     "ncn_field_bwd_dE_floats": [I64],
     "ncn_field_bwd": [P, P, I64, P, P, P, F32, F32, P, I32, P, P, P, P, P, P, P, P, P],
     "ncn_field_bwd_mlp": [P, P, I64, P, P, P, I32, P, P, P, P, P, P, P, P],
+    "ncn_field_bwd_mlp_din": [P, P, I64, P, P, P, I32, P, P, P, P, P, P, P, P, P, P],
+    "ncn_field_bwd_dx": [P, I64, P, P, P, P, F32, F32, P, P, P],
     "ncn_field_bwd_stash_floats": [I64],
     "ncn_field_bwd_part_blocks": [I64, I32],
     "ncn_field_reduce_wgrad_parts": [P, I32, I32, P, P],
@@ -69,6 +71,7 @@ SIGNATURES = {
     "ncn_field_reduce_wgrad": [P, I32, P, P],
     "ncn_normals_fwd": [P, P, P, P, P, P, I64, P, P],
     "ncn_normals_bwd": [P, P, P, P, P, P, I64, P, P, P, P],
+    "ncn_normals_bwd_rays": [P, P, P, P, P, P, I64, P, P, P, P, P, P],
     "ncn_photo_loss_fwd": [P, P, P, I64, F32, P, P],
     "ncn_photo_normals_fwd": [P, P, P, I64, F32, P, P, P, P, P, P, P, I64, P, P],
     "ncn_photo_normals_count_fwd": [P, P, P, I64, F32, P, P, P, P, P, P, P, I64, P, P, I64, P, P, P, P],

@@ -15,6 +15,10 @@ rounds with spherical renormalisation and faiss's split_clusters for empty clust
 RandomGenerator walk from a host-built std::mt19937 plan), then a final search over all points.
 faiss itself is not available here: parity unpinned w.r.t. faiss, see DESIGN.md §3.
 
+Pose refinement (train_nerf.py --optimize_ext: the prediction's rays require grad): `_Normals`
+back-propagates into rays_o / rays_d (`ncn_normals_bwd_rays`), NeRFMTLoss.forward then takes the
+unfused `_Normals` + `cluster_losses` branch, and the fused nodes, which stop at the depth, raise.
+
 Not provided (weight 0 in every reference config, hyperparameters.py:33-49): semantic,
 Manhattan-NeRF and the canonical-direction terms (raise if enabled).
 """
@@ -91,6 +95,15 @@ class _Normals(torch.autograd.Function):
     def backward(ctx, dn):
         rays_o, rays_d, depth, x1, x2, x3 = ctx.saved_tensors
         ddepth = torch.zeros_like(depth)
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            # pose refinement: the rays require grad (the reference's plain torch ops differentiate
+            # into them; with quirk q1, rays_o := rays_d, this is how the normal terms reach the poses)
+            d_o, d_d = torch.zeros_like(rays_o), torch.zeros_like(rays_d)
+            if dn is not None:
+                call("ncn_normals_bwd_rays", ptr(rays_o), ptr(rays_d), ptr(depth), ptr(x1), ptr(x2), ptr(x3),
+                     I64(x1.shape[0]), ptr(dn.contiguous().float()), None, ptr(ddepth), ptr(d_o), ptr(d_d), stream())
+            return (d_o if ctx.needs_input_grad[0] else None, d_d if ctx.needs_input_grad[1] else None, ddepth,
+                    None, None, None)
         if dn is not None:
             call("ncn_normals_bwd", ptr(rays_o), ptr(rays_d), ptr(depth), ptr(x1), ptr(x2), ptr(x3), I64(x1.shape[0]),
                  ptr(dn.contiguous()), None, ptr(ddepth), stream())
@@ -157,6 +170,14 @@ def cluster_losses(norm_depth, K=20, niter=20, seed=1234, t_similar=0.99, w=(1.0
     return _ClusterLoss.apply(norm_depth, K, niter, seed, t_similar, _weights_arg(w))
 
 
+def _no_ray_grad(rays_need_grad, who):
+    """The fused loss nodes back-propagate to the depth only: refuse rays that require grad (pose
+    refinement) instead of dropping their gradient."""
+    if rays_need_grad:
+        raise RuntimeError(f"{who} has no gradient w.r.t. rays_o / rays_d: with rays that require grad use "
+                           "extract_normals_from_ray_batch + cluster_losses (NeRFMTLoss does)")
+
+
 class _NormalsClusterLoss(torch.autograd.Function):
     """`_Normals` followed by `_ClusterLoss` as one node, used when the depth normals feed only the
     clustering terms (every reference config).  The backward is one `ncn_normals_bwd` launch that
@@ -165,6 +186,7 @@ class _NormalsClusterLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rays_o, rays_d, depth, x1, x2, x3, K, niter, seed, t_sim, w):
+        _no_ray_grad(ctx.needs_input_grad[0] or ctx.needs_input_grad[1], "normals_cluster_losses")
         T = x1.shape[0]
         dev = depth.device
         normals = torch.empty(T, 3, dtype=torch.float32, device=dev)
@@ -254,6 +276,7 @@ class _NeRFLossFused(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rgb, opacity, depth, rays_o, rays_d, rgb_gt, x1, x2, x3, w_op, K, niter, seed, t_sim, w,
                 step_dev, sched, count_job=None):
+        _no_ray_grad(ctx.needs_input_grad[3] or ctx.needs_input_grad[4], "the fused NeRFMTLoss node")
         R = rgb.shape[0]
         T = x1.shape[0]
         dev = rgb.device
@@ -468,7 +491,10 @@ class NeRFMTLoss(nn.Module):
             pred_w_gt["x123_idx"] = get_patch_triang_idx(n_w_gt, target_raw["patch_area"], off)
             pred_unsup["x123_idx"] = get_patch_triang_idx(n_unsup, target_raw["patch_area"], off)
         clustering = self.norm_D_C_ort_dot_w > 0 or self.norm_D_C_centr_dot_w > 0 or self.norm_D_C_centr_L1_w > 0
-        if (clustering and self.pred_norm_depth and unsup_start == 0 and self.opacity_w > 0 and self.distortion_w == 0
+        # pose refinement (the rays require grad): the unfused _Normals + cluster_losses branch, whose
+        # backward reaches the rays; the fused nodes stop at the depth
+        rays_grad = torch.is_grad_enabled() and (pred_raw["rays_o"].requires_grad or pred_raw["rays_d"].requires_grad)
+        if (not rays_grad and clustering and self.pred_norm_depth and unsup_start == 0 and self.opacity_w > 0 and self.distortion_w == 0
                 and self.ray_sampling_strategy in ("all_images_triang_patch", "same_image_triang_patch")
                 and self.depth_w == 0 and self.norm_DEpth_L1_w == 0 and self.norm_DEpth_dot_w == 0
                 and self.reg_depth_w == 0 and n_w_gt == pred_unsup["opacity"].shape[0] and n_w_gt % 64 == 0
@@ -479,7 +505,7 @@ class NeRFMTLoss(nn.Module):
             call("ncn_count_samples", ptr(job.total), I64(job.total.shape[0]), ptr(job.counter), ptr(job.out),
                  ptr(job.acc), stream())
         fuse_normals = (clustering and self.pred_norm_depth and unsup_start == 0 and self.norm_DEpth_L1_w == 0
-                        and self.norm_DEpth_dot_w == 0)
+                        and self.norm_DEpth_dot_w == 0 and not rays_grad)
         if self.pred_norm_depth and not fuse_normals:
             pred_w_gt["norm_depth"] = extract_normals_from_ray_batch(pred_w_gt["rays_o"], pred_w_gt["rays_d"],
                                                                      pred_w_gt["depth"], pred_w_gt["x123_idx"])

@@ -16,6 +16,14 @@ single RCCL call and the optimizer a single pass.  The backward accumulates stra
 `param.grad` (views of the flat gradient buffer): hash-table gradients by f32 atomics, weight
 gradients through a fixed-order slab reduction.
 
+Input gradients: `forward(x, d)` and `density(x)` are also differentiable w.r.t. x and d (tcnn's
+dL/dinput): the reference's --optimize_ext run (train_nerf.py:177-180, 244-249) makes the rays
+require grad, and RayMarcher.backward folds dL/dxyzs and dL/ddirs into them; d sigma / d x is the
+analytic normal.  dL/dd leaves the MLP backward, dL/dx is one more hash-grid gather
+(ncn_field_bwd_mlp_din / ncn_field_bwd_dx, no atomics: bit-identical run to run).  Under the
+internal fp16 GradScaler an overflowed backward leaves non-finite input gradients (the step the
+optimizer skips): the caller skips its pose update too.
+
 Not provided (off in every reference config, hyperparameters.py:26-30): pred_sem / pred_norm heads,
 rgb_act='None' exposure tonemappers.
 """
@@ -76,14 +84,21 @@ class _ParamHolder(nn.Module):
 
 
 class _FieldFunction(torch.autograd.Function):
-    """Fused hash-grid + sigma_net + TruncExp + rgb_net (ncn_field_fwd / ncn_field_bwd)."""
+    """Fused hash-grid + sigma_net + TruncExp + rgb_net (ncn_field_fwd / ncn_field_bwd).
+
+    Differentiable w.r.t. the three parameters (accumulated into the flat gradient buffer) and
+    w.r.t. the inputs x and d (camera pose refinement, density normals): dL/dd leaves the MLP pass
+    (ncn_field_bwd_mlp_din), dL/dx is a second hash-grid gather over the encoding gradient the MLP
+    pass left in its workspace (ncn_field_bwd_dx).  With every parameter frozen only the MLP pass
+    and the input kernels run: no table scatter, no weight-gradient reduction, flat_grad untouched."""
 
     @staticmethod
     def forward(ctx, x, d, table, w_sigma, w_rgb, model, mode, n_dev=None):
-        need_grad = any(ctx.needs_input_grad[2:5])  # grad mode is off inside Function.forward
+        need_grad = any(ctx.needs_input_grad[:5])  # grad mode is off inside Function.forward
         sigmas, rgbs, enc, packed, order = model._field_fwd(x, d, n_dev, mode, need_grad)
         if need_grad:
-            ctx.save_for_backward(x, d, enc, packed, n_dev, order)
+            need_in = ctx.needs_input_grad[0] or (d is not None and ctx.needs_input_grad[1])
+            ctx.save_for_backward(x, d, enc, packed, n_dev, order, table if need_in else None)
             ctx.model = model
         if mode != 0:
             ctx.mark_non_differentiable(rgbs)
@@ -92,27 +107,60 @@ class _FieldFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dL_dsigmas, dL_drgbs):
-        x, d, enc, packed, n_dev, order = ctx.saved_tensors
+        x, d, enc, packed, n_dev, order, table = ctx.saved_tensors
         model = ctx.model
         n = x.shape[0]
-        g_table, g_w = model._grad_views()
-        nb = _lib.lib().ncn_field_bwd_blocks(I64(n))
-        slab = torch.empty(nb * N_W, dtype=torch.float32, device=x.device)
-        dE_ws = torch.empty(int(_lib.lib().ncn_field_bwd_dE_floats(I64(n))), dtype=torch.float32, device=x.device)
+        dev = x.device
+        need_x = ctx.needs_input_grad[0]
+        need_d = d is not None and ctx.needs_input_grad[1]
+        need_param = any(ctx.needs_input_grad[2:5])
+        L = _lib.lib()
+        dE_ws = torch.empty(int(L.ncn_field_bwd_dE_floats(I64(n))), dtype=torch.float32, device=dev)
         c = lambda t: None if t is None else t.contiguous().float()
         dsig, drgb = c(dL_dsigmas), c(dL_drgbs)
-        if model.scatter_split is None:
-            call("ncn_field_bwd", ptr(x), ptr(d), I64(n), ptr(n_dev), ptr(order), model._levels_ptr, F32(model._xyz_min),
-                 F32(model._xyz_extent), ptr(packed), I32(model._prec), ptr(enc), ptr(dsig), ptr(drgb),
-                 ptr(model._bwd_loss_scale()), ptr(g_table), ptr(slab), ptr(dE_ws), ptr(model._level_max()), stream())
-        else:
+        scale = model._bwd_loss_scale()
+        g_table, g_w = model._grad_views() if need_param else (None, None)
+        dL_dx = dL_dd = None
+        if d is None:
+            # density mode (no directions): the sigma part alone on a zero stash, dL/dh = TruncExp'(h0) dL/dsigma
+            nb = int(L.ncn_field_bwd_part_blocks(I64(n), I32(2)))
+            slab = torch.empty(nb * N_W, dtype=torch.float32, device=dev)
+            stash = torch.zeros(int(L.ncn_field_bwd_stash_floats(I64(n))), dtype=torch.float32, device=dev)
             lmax = model._level_max()
-            call("ncn_field_bwd_mlp", ptr(x), ptr(d), I64(n), ptr(n_dev), ptr(order), ptr(packed), I32(model._prec), ptr(enc),
-                 ptr(dsig), ptr(drgb), ptr(model._bwd_loss_scale()),
-                 ptr(slab), ptr(dE_ws), ptr(lmax), stream())
-            model._scatter(x, n, n_dev, order, dE_ws, lmax, g_table)
-        call("ncn_field_reduce_wgrad", ptr(slab), I32(nb), ptr(g_w), stream())
-        return None, None, None, None, None, None, None, None
+            lmax.zero_()  # (the sigma part max-reduces into the rows the rgb part would have zeroed)
+            dE_ws[:4].zero_()  # (header: no permuted positions in this workspace)
+            call("ncn_field_bwd_mlp_part", ptr(x), ptr(None), I64(n), ptr(n_dev), ptr(order), ptr(packed), I32(model._prec),
+                 ptr(enc), ptr(dsig), ptr(None), ptr(None), ptr(scale), I32(2), I32(0), ptr(slab), ptr(dE_ws), ptr(lmax),
+                 ptr(stash), stream())
+            if need_param:
+                model._scatter(x, n, n_dev, order, dE_ws, lmax, g_table)
+                call("ncn_field_reduce_wgrad_parts", ptr(slab), I32(nb), I32(0), ptr(g_w), stream())
+        else:
+            nb = L.ncn_field_bwd_blocks(I64(n))
+            slab = torch.empty(nb * N_W, dtype=torch.float32, device=dev)
+            lmax = model._level_max()
+            if need_param and not (need_x or need_d) and model.scatter_split is None:
+                call("ncn_field_bwd", ptr(x), ptr(d), I64(n), ptr(n_dev), ptr(order), model._levels_ptr, F32(model._xyz_min),
+                     F32(model._xyz_extent), ptr(packed), I32(model._prec), ptr(enc), ptr(dsig), ptr(drgb),
+                     ptr(scale), ptr(g_table), ptr(slab), ptr(dE_ws), ptr(lmax), stream())
+            else:
+                if need_d:
+                    dL_dd = torch.empty(n, 3, dtype=torch.float32, device=dev)  # (the kernel zeroes rows >= *n_dev)
+                    call("ncn_field_bwd_mlp_din", ptr(x), ptr(d), I64(n), ptr(n_dev), ptr(order), ptr(packed), I32(model._prec),
+                         ptr(enc), ptr(dsig), ptr(drgb), ptr(scale), ptr(slab), ptr(dE_ws), ptr(lmax),
+                         ptr(model._flat[model._n_table:]), ptr(dL_dd), stream())
+                else:
+                    call("ncn_field_bwd_mlp", ptr(x), ptr(d), I64(n), ptr(n_dev), ptr(order), ptr(packed), I32(model._prec),
+                         ptr(enc), ptr(dsig), ptr(drgb), ptr(scale), ptr(slab), ptr(dE_ws), ptr(lmax), stream())
+                if need_param:
+                    model._scatter(x, n, n_dev, order, dE_ws, lmax, g_table)
+            if need_param:
+                call("ncn_field_reduce_wgrad", ptr(slab), I32(nb), ptr(g_w), stream())
+        if need_x:
+            dL_dx = torch.empty(n, 3, dtype=torch.float32, device=dev)  # (the kernel zeroes rows >= *n_dev)
+            call("ncn_field_bwd_dx", ptr(x), I64(n), ptr(n_dev), ptr(order), ptr(table), model._levels_ptr,
+                 F32(model._xyz_min), F32(model._xyz_extent), ptr(dE_ws), ptr(dL_dx), stream())
+        return dL_dx, dL_dd, None, None, None, None, None, None
 
 
 class NGPMT(nn.Module):
@@ -358,7 +406,8 @@ class NGPMT(nn.Module):
             self._deferred.append((x, n, n_dev, order, dE_ws, lmax, g_table))
 
     def density(self, x, return_feat=False):
-        """ngp_mt.py:157-171 (density-only kernel mode)."""
+        """ngp_mt.py:157-171 (density-only kernel mode).  Differentiable w.r.t. the parameters and
+        w.r.t. x (-d sigma / d x is the analytic normal): the sigma part of the MLP backward alone."""
         if return_feat:
             raise NotImplementedError("return_feat (the 16-d sigma_net feature) is only needed by the "
                                       "pred_sem/pred_norm heads, which are not provided")

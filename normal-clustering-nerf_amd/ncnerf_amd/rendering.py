@@ -11,6 +11,10 @@ kwargs['static_shapes']=True keeps every shape independent of the marched sample
 read of the counter), which is what lets Trainer capture the whole step in one HIP graph;
 kwargs['premarched'] (a march_train_static() result) skips intersect + march: the pipelined step
 marches the next batch while the current one is rendered.
+Pose refinement (train_nerf.py:177-180 --optimize_ext): with rays_o / rays_d that require grad the
+eager dynamic-shape path back-propagates to them (the field's dL/dxyzs and dL/ddirs through
+RayMarcher.backward; the loss's normals through results['rays_o'] / ['rays_d']); static_shapes or
+premarched then raise instead of dropping the gradient.
 """
 import time
 
@@ -27,6 +31,13 @@ def render(model, rays_o, rays_d, **kwargs):
     near_distance = kwargs["near_distance"]
     rays_o = rays_o.contiguous()
     rays_d = rays_d.contiguous()
+    if (torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad)
+            and not kwargs.get("test_time", False)):
+        # pose refinement (train_nerf.py --optimize_ext): the ray gradients come out of
+        # RayMarcher.backward, which needs the eager dynamic-shape march
+        if kwargs.get("static_shapes", False) or kwargs.get("premarched") is not None:
+            raise RuntimeError("render(): rays_o / rays_d require grad (pose refinement), which the static-shape / "
+                               "premarched path cannot back-propagate: call render() without static_shapes")
     if kwargs.get("premarched") is not None and not kwargs.get("test_time", False):
         return render_rays_train(model, rays_o, rays_d, None, **kwargs)
     if _fused_march_ok(model, kwargs, rays_o.shape[0]):  # intersect + jitter + march + scan + pack in one launch

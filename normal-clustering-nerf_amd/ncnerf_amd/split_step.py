@@ -74,6 +74,7 @@ def split_eligible(trainer, batch):
             and L.ray_sampling_strategy in ("all_images_triang_patch", "same_image_triang_patch")
             and L.depth_w == 0 and L.norm_DEpth_L1_w == 0 and L.norm_DEpth_dot_w == 0 and L.reg_depth_w == 0
             and R > 0 and R % 64 == 0 and R <= 16384 and batch["rgb"].shape[0] == R
+            and not batch["rays_o"].requires_grad and not batch["rays_d"].requires_grad  # (pose refinement: autograd)
             and all(v is not None for v in off.values()) and _standard_patch_offsets(batch.get("patch_area", 0), off)
             and not m.pred_norm and not m.pred_sem and getattr(m, "_aabb", None) is not None
             and kw.get("exp_step_factor", 0.0) == 0 and kw.get("anneal_strategy", "none") == "none"

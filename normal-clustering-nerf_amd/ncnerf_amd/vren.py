@@ -133,8 +133,10 @@ def raymarching_train_backward(dL_dxyzs, dL_ddirs, ts, rays_a):
     d_d = torch.empty(R, 3, dtype=torch.float32, device=ts.device)
     if R:
         # every segment end is another row's start or the last row's start + count: all must lie in [0, S]
+        # (one device-to-host read for the three bounds: this runs every step of a pose-refining run)
         st = rays_a[:, 1]
-        lo, hi = int(st.min()), max(int(st.max()), int(rays_a[-1, 1] + rays_a[-1, 2]))
+        lo, hi_start, hi_end = torch.stack([st.min(), st.max(), rays_a[-1, 1] + rays_a[-1, 2]]).cpu().tolist()
+        hi = max(hi_start, hi_end)
         if lo < 0 or hi > S:
             raise RuntimeError(f"rays_a segments reach outside the {S} samples ([{lo}, {hi}))")
     call("ncn_segment_csr", ptr(dL_dxyzs), ptr(dL_ddirs), ptr(ts), ptr(rays_a), I64(R), ptr(d_o), ptr(d_d), stream())
