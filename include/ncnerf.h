@@ -466,6 +466,39 @@ int ncn_nerf_loss_bwd(const float* rgb, const float* rgb_gt, const float* opacit
                       const float* dL_dnormals, const float* up_total, const float* up_terms, float* dL_drgb,
                       float* dL_dopacity, float* dL_ddepth, void* stream);
 
+/* ---- Manhattan-frame evaluation (validation_step / validation_epoch_end, train_nerf.py:381-534):
+ *      normals of whole depth images and faiss's spherical k-means over any number of them. ---- */
+/* _extract_normals_from_depth_batch (datasets/hypersim_src/utils.py:544-611): depth (B,H,W), dirs_cc
+ * (H*W,3) camera-space ray directions, rot (B,3,3) row-major camera-to-world rotations -> normals
+ * (B,H,W,3).  P = dirs_cc * depth; n = rot . normalize(cross(P[y-1,x] - P[y,x], P[y,x-1] - P[y,x]))
+ * (F.normalize's max(|.|, 1e-12)).  The 1-pixel border and every pixel whose own depth is 0, NaN or
+ * Inf are zero; a pixel with a non-finite neighbour is NaN, as in the reference.  Every element of
+ * normals is written. */
+int ncn_depth_normals_image(const float* depth, const float* dirs_cc, const float* rot, int B, int H, int W,
+                            float* normals, void* stream);
+/* The random draws of faiss's Clustering::train for nx valid points (host only; K <= 32, K <= nx <
+ * 2^31): sub_idx (min(nx, 256 K) int64) = the training set as indices into the points, in training
+ * order (the identity up to 256 K points, else the first 256 K entries of rand_perm(nx, seed));
+ * init_idx (K int64) = the initial centroids as indices into the points (rand_perm(|train|, seed +
+ * 1)[:K] composed with sub_idx); init_rows (K int64, or NULL) = the same picks as rows of the
+ * training set (sub_idx[init_rows[k]] == init_idx[k]): what ncn_kmeans_train's init_idx takes.
+ * O(K) memory whatever nx is. */
+int ncn_kmeans_draws(int64_t nx, int K, uint32_t seed, int64_t* sub_idx, int64_t* init_idx, int64_t* init_rows);
+/* split_clusters' RandomGenerator(seed).rand_float() sequence, n floats (host only). */
+int ncn_kmeans_rand_floats(uint32_t seed, int n, float* host_out);
+/* The Lloyd rounds of faiss.Kmeans(3, K, niter, spherical=True).train on the training set, ONE
+ * workgroup (no co-residency requirement): train_pts (nt,3) valid unit normals, K <= nt <= 256 K,
+ * K <= 32, niter <= 64; init_idx (K int64 device) rows of train_pts; rand_floats (4096 device floats)
+ * = ncn_kmeans_rand_floats(1234, 4096); -> centroids (K,3).  nt == K is faiss's corner case: the
+ * points themselves, unnormalised, init_idx not read.  Bit-reproducible (exact integer sums).
+ * A round whose split walk needs more than the 4096 floats writes NaN centroids. */
+int ncn_kmeans_train(const float* train_pts, int nt, int K, int niter, const int64_t* init_idx,
+                     const float* rand_floats, float* centroids, void* stream);
+/* kmeans.index.search(pts, 1): assign (n int32) = argmax_k <pts_i, centroids_k> (ties: lowest k),
+ * counts (K int64, zeroed here) = the cluster sizes.  Any n. */
+int ncn_kmeans_assign(const float* pts, int64_t n, const float* centroids, int K, int32_t* assign, int64_t* counts,
+                      void* stream);
+
 /* ---- step inputs (train_nerf.py:208: the batch handed to training_step): copies n_bufs <= 8 device
  *      buffers (src[b] -> dst[b], n_bytes[b]; HOST arrays of device pointers), writes `step` to
  *      *step_dst and `flag` to *flag_dst (either may be NULL) in ONE launch — the new batch into a

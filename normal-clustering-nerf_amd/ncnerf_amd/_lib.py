@@ -95,6 +95,11 @@ SIGNATURES = {
     "ncn_grid_sample": [P, I64, I32, F32, F32, F32, I64, I32, U64, F32, P, P, P, P, P, P],
     "ncn_grid_apply": [P, P, P, P, I64, F32, P, P],
     "ncn_grid_packbits": [P, I64, F64, P, P, P, P],
+    "ncn_depth_normals_image": [P, P, P, I32, I32, I32, P, P],
+    "ncn_kmeans_draws": [I64, I32, U32, P, P, P],
+    "ncn_kmeans_rand_floats": [U32, I32, P],
+    "ncn_kmeans_train": [P, I32, I32, I32, P, P, P, P],
+    "ncn_kmeans_assign": [P, I64, P, I32, P, P, P],
 }
 
 _lib = None
