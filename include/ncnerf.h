@@ -499,6 +499,45 @@ int ncn_kmeans_train(const float* train_pts, int nt, int K, int niter, const int
 int ncn_kmeans_assign(const float* pts, int64_t n, const float* centroids, int K, int32_t* assign, int64_t* counts,
                       void* stream);
 
+/* ---- device-resident training data (datasets/base.py:142-182, train_nerf.py:165-182): the batch is
+ *      drawn and its rays are generated on the device; no host read, capturable. ---- */
+#define NCN_CORNER_REFERENCE 0 /* pixel = corner ordinal + iy W + ix (base.py:164-166) */
+#define NCN_CORNER_GRID 1      /* pixel = (corner row + iy) W + corner column + ix */
+#define NCN_IMAGE_F32 0
+#define NCN_IMAGE_U8 1 /* read as (float)u / 255.0f */
+/* BaseDataset.__getitem__ for `all_images_triang_patch` / `same_image_triang_patch` (base.py:142-167):
+ * n_patches patches of patch x patch pixels -> img_idxs, pix_idxs (n_patches patch^2 int64, patch
+ * after patch, cells row-major).  Counter-based draws instead of numpy's global generator: with
+ * z(k) = splitmix64's output k under `seed`, and the counter k(step, r) = step * 0x100000001B3 + r,
+ * patch p takes image umulhi(z(k(step, 1 + 2p)), n_images) and corner ordinal c =
+ * umulhi(z(k(step, 2 + 2p)), (H-patch+1)(W-patch+1)); same_image != 0: every patch takes image
+ * umulhi(z(k(step, 0)), n_images).  step = *step_dev (device int64), or `step` when step_dev is NULL.
+ * Cell (iy, ix) is pixel c + iy W + ix with NCN_CORNER_REFERENCE (the reference adds the offsets to
+ * the corner's ordinal: patches wrap over row ends, the largest pixel is H W - 1 - (patch-1)(H-patch)),
+ * or (c / (W-patch+1) + iy) W + c % (W-patch+1) + ix with NCN_CORNER_GRID. */
+int ncn_batch_draw(uint64_t seed, const int64_t* step_dev, int64_t step, int n_images, int H, int W, int patch,
+                   int64_t n_patches, int same_image, int corner_mode, int64_t* img_idxs, int64_t* pix_idxs,
+                   void* stream);
+/* rays[img_idxs, pix_idxs] (base.py:176-177) and NeRFSystem.forward's ray code (train_nerf.py:167-182:
+ * poses[img_idxs], directions[pix_idxs], axisangle_to_R, get_rays), one thread per ray.  images
+ * (n_images, n_pixels, 3) float or uint8 (image_dtype), directions (n_pixels, 3), poses (n_images, 3, 4),
+ * dR / dT (n_images, 3) or both NULL -> rays_o, rays_d, rgb (n_rays, 3) float.  rays_d = (A(dR[i]) R_i) dir, rays_o = t_i + dT[i], A = axisangle_to_R
+ * (ray_utils.py:75-101: theta = |v| + 1e-7) with (1 - cos theta) / theta^2 evaluated as
+ * sinc(theta/2)^2 / 2, accurate at the |v| ~ 1e-6 the parameter takes.  dR = dT = NULL: the stored
+ * pose; rgb and rays_o are then copies.  An index out of range gives NaN in its ray. */
+int ncn_batch_rays_fw(const int64_t* img_idxs, const int64_t* pix_idxs, int64_t n_rays, const void* images,
+                      int image_dtype, const float* directions, const float* poses, const float* dR, const float* dT,
+                      int n_images, int64_t n_pixels, float* rays_o, float* rays_d, float* rgb, void* stream);
+/* The backward of ncn_batch_rays_fw into the pose corrections (autograd of train_nerf.py:177-182 into
+ * self.dR / self.dT): grad_dT[i] = sum of dL_drays_o over image i's rays, grad_dR[i] = <sum dL_drays_d
+ * (x) (R_i dir), dA/dv> with d theta / dv = v / |v|, 0 at v = 0 (torch.norm's convention).  Every row
+ * of grad_dR / grad_dT (n_images, 3) is written (zeros for images without rays: no memset before it).
+ * One workgroup per image sums in a fixed order: no float atomics, bit-reproducible, any order of
+ * img_idxs. */
+int ncn_batch_rays_bw(const float* dL_drays_o, const float* dL_drays_d, const int64_t* img_idxs,
+                      const int64_t* pix_idxs, int64_t n_rays, const float* directions, const float* poses,
+                      const float* dR, int n_images, int64_t n_pixels, float* grad_dR, float* grad_dT, void* stream);
+
 /* ---- step inputs (train_nerf.py:208: the batch handed to training_step): copies n_bufs <= 8 device
  *      buffers (src[b] -> dst[b], n_bytes[b]; HOST arrays of device pointers), writes `step` to
  *      *step_dst and `flag` to *flag_dst (either may be NULL) in ONE launch — the new batch into a

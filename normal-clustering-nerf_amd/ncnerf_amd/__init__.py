@@ -11,4 +11,4 @@ All compute goes through libncnerf.so (C ABI: include/ncnerf.h); there is no CPU
 from . import _lib  # noqa: F401
 
 __all__ = ["vren", "custom_functions", "rendering", "ngp_mt", "losses", "optim", "trainer", "synthetic",
-           "distributed", "evaluation"]
+           "distributed", "evaluation", "data"]

@@ -100,6 +100,9 @@ SIGNATURES = {
     "ncn_kmeans_rand_floats": [U32, I32, P],
     "ncn_kmeans_train": [P, I32, I32, I32, P, P, P, P],
     "ncn_kmeans_assign": [P, I64, P, I32, P, P, P],
+    "ncn_batch_draw": [U64, P, I64, I32, I32, I32, I32, I64, I32, I32, P, P, P],
+    "ncn_batch_rays_fw": [P, P, I64, P, I32, P, P, P, P, I32, I64, P, P, P, P],
+    "ncn_batch_rays_bw": [P, P, P, P, I64, P, P, P, I32, I64, P, P, P],
 }
 
 _lib = None
