@@ -14,6 +14,16 @@
  * Layout conventions: float3 arrays are AoS (N,3) contiguous as in the reference; rays_a is (R,3)
  * int64 (ray_idx, start, n_samples) in RAY ORDER (the reference's atomic order is
  * nondeterministic, raymarching.cu:237-238).
+ *
+ * THIS FILE IS PARSED: ncnerf_amd/_lib.py derives the ctypes binding (argtypes, restype, and the
+ * argument checks of _lib.call) from the declarations below, so they keep to this grammar —
+ * `ret name(type param, ...);` with every parameter named (or `(void)`); ret one of int, int64_t,
+ * const char*; scalar parameters int, int32_t, int64_t, uint32_t, uint64_t, float, double; pointer
+ * parameters (const or not) to void, float, double, int, int32_t, int64_t, uint8_t, uint16_t,
+ * uint32_t, and void** for host arrays of pointers.  A launching function's last parameter is
+ * `void* stream`; one without it is host code.  Comments and preprocessor lines (no continuation
+ * lines) are skipped; anything else — another type, an unnamed parameter, a function pointer, a
+ * struct — makes the import fail (tests/test_abi.py).
  */
 #ifndef NCNERF_H
 #define NCNERF_H

@@ -1,16 +1,22 @@
-"""ctypes binding of libncnerf.so (the C ABI declared in include/ncnerf.h).
+"""ctypes binding of libncnerf.so, derived from the C ABI declared in include/ncnerf.h.
 
 This is the only place Python talks to the HIP kernels.  There is NO CPU fallback: if the library
 is missing, or a kernel is called with a CPU tensor, the call raises.  Tensors are passed as raw
 device pointers and sizes, on torch's *current* HIP stream (never the legacy default stream).
+
+The header is the single statement of the ABI: parsed at import, it gives every argtypes / restype,
+and `call` marshals plain arguments against it (see `marshal`) before anything is launched.
 """
 import ctypes
+import operator
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NCN_LIB_PATH") or os.path.join(_HERE, "libncnerf.so")  # (override: diagnostics)
+HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "ncnerf.h")
 
 P = ctypes.c_void_p
 I64 = ctypes.c_int64
@@ -21,89 +27,74 @@ F64 = ctypes.c_double
 AMP_INIT_SCALE = 65536.0  # NCN_AMP_INIT_SCALE (include/ncnerf.h): torch GradScaler's init_scale
 U64 = ctypes.c_uint64
 
-# name -> argtypes (stream last); every function returns int (hipError_t)
-SIGNATURES = {
-    "ncn_grad_pack_f16": [P, I64, P, I32, P, P],
-    "ncn_grad_unpack_f16": [P, I64, P, P, P],
-    "ncn_morton3D": [P, I64, P, P],
-    "ncn_morton3D_invert": [P, I64, P, P],
-    "ncn_packbits": [P, I64, F32, P, P],
-    "ncn_ray_aabb_intersect": [P, P, I64, P, P, I64, I32, P, P, P, P],
-    "ncn_ray_aabb_intersect_near": [P, P, I64, P, P, I64, I32, F32, P, P, P, P],
-    "ncn_march_train_walk": [P, P, P, P, I64, P, I32, F32, F32, I32, I32, P, P, P, P, P],
-    "ncn_march_train_scan": [P, I64, P, P, P],
-    "ncn_march_train_fused_work_bytes": [I64],
-    "ncn_march_train_fused": [P, P, I64, F32, F32, F32, F32, F32, F32, F32, P, U64, P, P, I32, F32, I32, I32, P, P, P,
-                              P, P, P, P, P, P, P, P],
-    "ncn_march_train_pack": [P, P, I64, I32, P, P, P, P, P, P, P, P],
-    "ncn_segment_csr": [P, P, P, P, I64, P, P, P],
-    "ncn_march_test": [P, P, P, P, I64, P, I32, F32, F32, I32, I32, I32, P, P, P, P, P, P],
-    "ncn_composite_train_fw": [P, P, P, P, P, I64, I64, I32, F32, P, P, P, P, P, P],
-    "ncn_composite_train_bw": [P, P, P, P, P, P, P, P, P, P, I64, I64, I32, P, P, P, F32, P, P, P],
-    "ncn_composite_train_fw_bg": [P, P, P, P, P, I64, I64, I32, F32, P, P, P, P, P, F32, P, P],
-    "ncn_count_samples": [P, I64, P, P, P, P],
-    "ncn_step_inputs": [I32, P, P, P, P, I64, P, I32, P],
-    "ncn_composite_train_bw_bg": [P, P, P, P, P, P, P, P, P, P, I64, I64, I32, P, P, P, F32, F32, P, P, P],
-    "ncn_test_compact": [P, P, P, I64, I32, P, P, P, P, P],
-    "ncn_composite_test_fw_compact": [P, P, P, P, P, P, I64, I32, I32, F32, P, P, P, P, P],
-    "ncn_test_loop_march": [P, P, P, P, I64, P, I32, F32, F32, I32, I32, P, P, P, P, P, P, P],
-    "ncn_test_loop_index": [P, I64, P, P, P],
-    "ncn_test_loop_composite": [P, P, P, P, P, P, I64, P, I32, F32, P, P, P, P, P],
-    "ncn_test_loop_next": [P, P, I64, P, P, I32, I32, I32, P],
-    "ncn_composite_test_fw": [P, P, P, P, P, I64, I32, I32, F32, P, P, P, P, P],
-    "ncn_field_pack_weights": [P, P, I32, P],
-    "ncn_field_pack_map": [P, P],
-    "ncn_field_sort_windows": [P, I64, P, F32, F32, P, P],
-    "ncn_field_fwd": [P, P, I64, P, P, P, P, F32, F32, P, I32, I32, P, P, P, P],
-    "ncn_field_bwd_blocks": [I64],
-    "ncn_field_bwd_dE_floats": [I64],
-    "ncn_field_bwd": [P, P, I64, P, P, P, F32, F32, P, I32, P, P, P, P, P, P, P, P, P],
-    "ncn_field_bwd_mlp": [P, P, I64, P, P, P, I32, P, P, P, P, P, P, P, P],
-    "ncn_field_bwd_mlp_din": [P, P, I64, P, P, P, I32, P, P, P, P, P, P, P, P, P, P],
-    "ncn_field_bwd_dx": [P, I64, P, P, P, P, F32, F32, P, P, P],
-    "ncn_field_bwd_stash_floats": [I64],
-    "ncn_field_bwd_part_blocks": [I64, I32],
-    "ncn_field_reduce_wgrad_parts": [P, I32, I32, P, P],
-    "ncn_field_bwd_mlp_part": [P, P, I64, P, P, P, I32, P, P, P, P, P, I32, I32, P, P, P, P, P],
-    "ncn_field_scatter_positions": [P, I64, P, P, P],
-    "ncn_field_scatter": [P, I64, P, P, P, F32, F32, P, P, I32, I32, I32, P, P],
-    "ncn_field_scatter_wgrad": [P, I64, P, P, P, F32, F32, P, P, I32, I32, I32, P, P, I32, I32, P, P],
-    "ncn_field_reduce_wgrad": [P, I32, P, P],
-    "ncn_normals_fwd": [P, P, P, P, P, P, I64, P, P],
-    "ncn_normals_bwd": [P, P, P, P, P, P, I64, P, P, P, P],
-    "ncn_normals_bwd_rays": [P, P, P, P, P, P, I64, P, P, P, P, P, P],
-    "ncn_photo_loss_fwd": [P, P, P, I64, F32, P, P],
-    "ncn_photo_normals_fwd": [P, P, P, I64, F32, P, P, P, P, P, P, P, I64, P, P],
-    "ncn_photo_normals_count_fwd": [P, P, P, I64, F32, P, P, P, P, P, P, P, I64, P, P, I64, P, P, P, P],
-    "ncn_photo_loss_bwd": [P, P, P, I64, F32, P, P, P, P, P],
-    "ncn_cluster_workspace_words": [I32],
-    "ncn_cluster_status_offset": [I32],
-    "ncn_cluster_coresidency": [I32, I32, P],
-    "ncn_kmeans_plan_words": [I32, I32],
-    "ncn_kmeans_plan_fill": [I32, I32, U32, P],
-    "ncn_cluster_loss": [P, I64, I32, I32, P, F32, F32, F32, F32, P, P, F32, F32, P, P, P, P, P, P, P],
-    "ncn_nerf_loss_bwd": [P, P, P, I64, F32, P, P, P, P, P, P, P, P, P, P, P],
-    "ncn_sumsq": [P, I64, P, P, P],
-    "ncn_adam": [P, P, P, P, I64, P, F32, F32, F32, F32, F32, F32, I32, P, P, P],
-    "ncn_adam_step": [P, P, P, P, I64, I64, F32, F32, F32, F64, F64, F32, F32, F32, P, P, P, I32, P, P, P],
-    "ncn_adam_step_packed": [P, P, P, P, I64, I64, F32, F32, F32, F64, F64, F32, F32, F32, P, P, P, I32, P, P,
-                             P, I64, P, I32, P],
-    "ncn_adam_step_work_floats": [],
-    "ncn_distortion_loss_fw": [P, P, P, P, I64, P, P, P, P],
-    "ncn_distortion_loss_bw": [P, P, P, P, P, P, P, I64, P, P],
-    "ncn_grid_work_bytes": [],
-    "ncn_grid_sample": [P, I64, I32, F32, F32, F32, I64, I32, U64, F32, P, P, P, P, P, P],
-    "ncn_grid_apply": [P, P, P, P, I64, F32, P, P],
-    "ncn_grid_packbits": [P, I64, F64, P, P, P, P],
-    "ncn_depth_normals_image": [P, P, P, I32, I32, I32, P, P],
-    "ncn_kmeans_draws": [I64, I32, U32, P, P, P],
-    "ncn_kmeans_rand_floats": [U32, I32, P],
-    "ncn_kmeans_train": [P, I32, I32, I32, P, P, P, P],
-    "ncn_kmeans_assign": [P, I64, P, I32, P, P, P],
-    "ncn_batch_draw": [U64, P, I64, I32, I32, I32, I32, I64, I32, I32, P, P, P],
-    "ncn_batch_rays_fw": [P, P, I64, P, I32, P, P, P, P, I32, I64, P, P, P, P],
-    "ncn_batch_rays_bw": [P, P, P, P, I64, P, P, P, I32, I64, P, P, P],
-}
+
+class NcnError(RuntimeError):
+    pass
+
+
+# The grammar of include/ncnerf.h (stated at its top): `ret name(type name, ...);` over these types.
+_RESTYPES = {"int": ctypes.c_int, "int64_t": I64, "const char*": ctypes.c_char_p}
+_SCALARS = {"int": I32, "int32_t": I32, "int64_t": I64, "uint32_t": U32, "uint64_t": U64, "float": F32, "double": F64}
+_POINTEES = {"void": 0, "float": 4, "double": 8, "int": 4, "int32_t": 4, "int64_t": 8, "uint8_t": 1, "uint16_t": 2,
+             "uint32_t": 4}
+_DECL = re.compile(r"(const\s+char\s*\*|int64_t|int)\s*(\w+)\s*\(([^()]*)\)")
+_PARAM = re.compile(r"(?:const\s+)?(\w+)(?:\s*((?:\*\s*(?:const\b\s*)?)+)|\s+)(\w+)")
+
+
+def parse_header(text):
+    """{name: (restype, [(kind, pointee_bytes, param_name), ...])} of every declaration of a C header
+    in ncnerf.h's grammar.  restype and a scalar's kind are the C type's name; a pointer's kind is
+    "ptr" and pointee_bytes the width of what it points to (0 for void, 8 for a pointer).  Anything
+    outside the grammar is a ValueError naming the declaration: nothing is guessed."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    if re.search(r"^\s*#.*\\$", text, flags=re.M):
+        raise ValueError("ncnerf.h grammar: a preprocessor line is continued with a backslash")
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+    text, n_extern = re.subn(r'extern\s+"C"\s*\{', "", text)
+    text = text.strip()
+    if n_extern == 1 and text.endswith("}"):
+        text = text[:-1]
+    *decls, rest = text.split(";")
+    if rest.strip():
+        raise ValueError(f"ncnerf.h grammar: no ';' after {' '.join(rest.split())!r}")
+    out = {}
+    for decl in decls:
+        decl = " ".join(decl.split())
+        m = _DECL.fullmatch(decl)
+        if m is None:
+            raise ValueError(f"ncnerf.h grammar: not `int|int64_t|const char* name(params)`: {decl!r}")
+        ret, name, params = m.groups()
+        if name in out:
+            raise ValueError(f"ncnerf.h grammar: {name} is declared twice")
+        plist = []
+        for p in ([] if params.strip() in ("", "void") else params.split(",")):
+            pm = _PARAM.fullmatch(p.strip())
+            if pm is None or pm.group(3) in _POINTEES or pm.group(3) in _SCALARS or pm.group(3) == "const":
+                raise ValueError(f"ncnerf.h grammar: parameter {p.strip()!r} of {decl!r} is not `type name`")
+            base, stars, pname = pm.group(1), (pm.group(2) or "").count("*"), pm.group(3)
+            if stars == 0 and base in _SCALARS:
+                plist.append((base, 0, pname))
+            elif stars == 1 and base in _POINTEES:
+                plist.append(("ptr", _POINTEES[base], pname))
+            elif stars == 2 and base == "void":
+                plist.append(("ptr", 8, pname))
+            else:
+                raise ValueError(f"ncnerf.h grammar: unknown type in parameter {p.strip()!r} of {decl!r}")
+        out[name] = ("const char*" if ret.startswith("const") else ret, plist)
+    return out
+
+
+def _read_header():
+    try:
+        return open(HEADER_PATH).read()
+    except OSError as e:
+        raise NcnError(f"include/ncnerf.h not found at {HEADER_PATH}: the binding is derived from it ({e})") from None
+
+
+ABI = parse_header(_read_header())
+# name -> argtypes (stream last), as ctypes sees them
+SIGNATURES = dict((name, [P if kind == "ptr" else _SCALARS[kind] for kind, _, _ in params])
+                  for name, (_, params) in ABI.items())
 
 _lib = None
 
@@ -116,10 +107,6 @@ TIMING = None
 TIMING_SPIN_CYCLES = 60000
 
 
-class NcnError(RuntimeError):
-    pass
-
-
 def lib():
     """Load libncnerf.so (after torch's HIP runtime, so both share one libamdhip64)."""
     global _lib
@@ -128,30 +115,97 @@ def lib():
             raise NcnError(f"libncnerf.so not found at {LIB_PATH}: run __graft_entry__.build() "
                            f"(make -C normal-clustering-nerf_amd)")
         L = ctypes.CDLL(LIB_PATH)
-        for name, args in SIGNATURES.items():
+        for name, (ret, _) in ABI.items():
             fn = getattr(L, name)
-            fn.argtypes = args
-            fn.restype = ctypes.c_int
-        L.ncn_cluster_workspace_words.restype = ctypes.c_int64
-        L.ncn_cluster_status_offset.restype = ctypes.c_int64
-        L.ncn_kmeans_plan_words.restype = ctypes.c_int64
-        L.ncn_field_bwd_dE_floats.restype = ctypes.c_int64
-        L.ncn_field_bwd_stash_floats.restype = ctypes.c_int64
-        L.ncn_adam_step_work_floats.restype = ctypes.c_int64
-        L.ncn_grid_work_bytes.restype = ctypes.c_int64
-        L.ncn_march_train_fused_work_bytes.restype = ctypes.c_int64
-        L.ncn_last_error.argtypes = []
-        L.ncn_last_error.restype = ctypes.c_char_p
-        L.ncn_version.restype = ctypes.c_int
+            fn.argtypes = SIGNATURES[name]
+            fn.restype = _RESTYPES[ret]
         _lib = L
     return _lib
 
 
 def exported_symbols():
-    return list(SIGNATURES) + ["ncn_last_error", "ncn_version"]
+    return list(ABI)
+
+
+# ---- marshalling: one function per entry point, generated once from the header's parameters
+# (straight-line code: a Python call per argument costs more than the wrappers it replaces) ----
+_Tensor = torch.Tensor
+_CTYPES = (ctypes.c_int.__mro__[-2], type(ctypes.byref(ctypes.c_int())))  # _CData, and what byref() returns
+_AUTO = object()  # the omitted stream
+
+
+def _launches(params):
+    return bool(params) and params[-1] == ("ptr", 0, "stream")
+
+
+def _refuse(name, i, a):
+    params = ABI[name][1]
+    kind, width, pname = params[i]
+    expected = f"a host {kind}" if kind != "ptr" else (
+        f"a {'CUDA ' if _launches(params) else ''}tensor{' of %d-byte elements' % width if width else ''}, "
+        f"None or a ctypes pointer")
+    got = f"a {a.dtype} {a.device.type} tensor" if isinstance(a, _Tensor) else f"{type(a).__name__} {a!r}"
+    raise TypeError(f"{name}: argument {i} ({pname}) takes {expected}, got {got}")
+
+
+def _number(name, i, a, convert):
+    """An int / float parameter's value that is neither an exact int / float nor a ctypes instance: never a
+    device tensor into a host number (that would hide a synchronisation), and float() would parse a str."""
+    if isinstance(a, (_Tensor, str, bytes, bytearray)):
+        _refuse(name, i, a)
+    try:
+        return convert(a)
+    except TypeError:
+        _refuse(name, i, a)
+
+
+def _marshal_source(name, params):
+    launches = _launches(params)
+    n = len(params)
+    src = [f"def marshal({', '.join(f'a{i}' for i in range(n))}{'=_AUTO' if launches else ''}):"]
+    for i, (kind, width, _) in enumerate(params):
+        a = f"a{i}"
+        if kind == "ptr":
+            bad = ([f"{a}.element_size() != {width}"] if width else []) + ([f"not {a}.is_cuda"] if launches else [])
+            auto = launches and i == n - 1
+            src += [f" if {a} is _AUTO: {a} = stream()"] if auto else []
+            src += [f" {'el' if auto else ''}if isinstance({a}, _Tensor):"]
+            src += [f"  if {' or '.join(bad)}: _refuse({name!r}, {i}, {a})"] if bad else []
+            src += [f"  {a} = {a}.data_ptr()",
+                    f" elif {a} is not None and not isinstance({a}, _CTYPES): _refuse({name!r}, {i}, {a})"]
+        else:
+            exact, convert = ("float", "float") if kind in ("float", "double") else ("int", "operator.index")
+            src += [f" if type({a}) is not {exact} and not isinstance({a}, _CTYPES):"
+                    f" {a} = _number({name!r}, {i}, {a}, {convert})"]
+    src += [f" return ({''.join(f'a{i}, ' for i in range(n))})"]
+    return "\n".join(src)
+
+
+def _marshaller(name, params):
+    ns = {}
+    exec(_marshal_source(name, params), globals(), ns)  # globals(): `stream` is looked up when the call is made
+    n = len(params)
+    return ns["marshal"], (n - 1, n) if _launches(params) else (n,)
+
+
+_PLANS = {name: _marshaller(name, params) for name, (_, params) in ABI.items()}
+
+
+def marshal(name, args):
+    """The argument tuple `call` hands to ctypes.  Per declared parameter: a ctypes instance passes
+    untouched; a pointer takes None or a tensor (of the pointee's width unless that is void; a CUDA
+    tensor when the function takes a stream, i.e. launches); an integer takes operator.index(x), a
+    float float(x), never a tensor.  A function whose last parameter is `void* stream` may be given
+    without it: the current stream is appended, after every check.  Anything else is a TypeError."""
+    fn, counts = _PLANS[name]
+    if len(args) not in counts:
+        decl = ", ".join(f"{'pointer' if kind == 'ptr' else kind} {pname}" for kind, _, pname in ABI[name][1])
+        raise TypeError(f"{name}: takes {' or '.join(map(str, counts))} arguments, got {len(args)}: {name}({decl})")
+    return fn(*args)
 
 
 def call(name, *args):
+    args = marshal(name, args)
     if TIMING is not None and name in TIMING:
         e0 = torch.cuda.Event(enable_timing=True)
         e1 = torch.cuda.Event(enable_timing=True)
@@ -187,8 +241,7 @@ def step_inputs(srcs, dsts, step_dev, step, flag_dev=None, flag=0):
     src = VP(*[s.data_ptr() for s in srcs])
     dst = VP(*[d.data_ptr() for d in dsts])
     nb = (ctypes.c_int64 * max(n, 1))(*[s.numel() * s.element_size() for s in srcs])
-    return call("ncn_step_inputs", I32(n), ctypes.cast(src, P), ctypes.cast(dst, P), ctypes.cast(nb, P),
-                ptr(step_dev), I64(int(step)), ptr(flag_dev), I32(int(flag)), stream())
+    return call("ncn_step_inputs", n, src, dst, nb, step_dev, int(step), flag_dev, int(flag))
 
 
 def check_input(t, name):

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import I32, I64, U64, call, ptr, stream
+from ._lib import call
 
 STRATEGIES = ("all_images_triang_patch", "same_image_triang_patch")
 CORNER_MODES = {"reference": 0, "grid": 1}  # NCN_CORNER_REFERENCE / NCN_CORNER_GRID
@@ -40,23 +40,20 @@ def batch_draw(seed, step, n_images, H, W, patch, n_patches, same_image, corner_
         step_dev, step_host = step, 0
     else:
         step_dev, step_host = None, int(step)
-    call("ncn_batch_draw", U64(int(seed) & (2 ** 64 - 1)), ptr(step_dev), I64(step_host), I32(n_images), I32(H), I32(W),
-         I32(patch), I64(n_patches), I32(1 if same_image else 0), I32(corner_mode), ptr(img_idxs), ptr(pix_idxs),
-         stream())
+    call("ncn_batch_draw", int(seed) & (2 ** 64 - 1), step_dev, step_host, n_images, H, W,
+         patch, n_patches, 1 if same_image else 0, corner_mode, img_idxs, pix_idxs)
 
 
 def batch_rays_fw(img_idxs, pix_idxs, images, directions, poses, dR, dT, rays_o, rays_d, rgb):
     """ncn_batch_rays_fw; dR = dT = None: the stored poses."""
-    call("ncn_batch_rays_fw", ptr(img_idxs), ptr(pix_idxs), I64(img_idxs.numel()), ptr(images),
-         I32(_IMAGE_DTYPES[images.dtype]), ptr(directions), ptr(poses), ptr(dR), ptr(dT),
-         I32(poses.shape[0]), I64(directions.shape[0]), ptr(rays_o), ptr(rays_d), ptr(rgb), stream())
+    call("ncn_batch_rays_fw", img_idxs, pix_idxs, img_idxs.numel(), images, _IMAGE_DTYPES[images.dtype], directions,
+         poses, dR, dT, poses.shape[0], directions.shape[0], rays_o, rays_d, rgb)
 
 
 def batch_rays_bw(g_o, g_d, img_idxs, pix_idxs, directions, poses, dR, grad_dR, grad_dT):
     """ncn_batch_rays_bw: every row of grad_dR / grad_dT (V,3) is written."""
-    call("ncn_batch_rays_bw", ptr(g_o), ptr(g_d), ptr(img_idxs), ptr(pix_idxs), I64(img_idxs.numel()),
-         ptr(directions), ptr(poses), ptr(dR), I32(poses.shape[0]), I64(directions.shape[0]), ptr(grad_dR),
-         ptr(grad_dT), stream())
+    call("ncn_batch_rays_bw", g_o, g_d, img_idxs, pix_idxs, img_idxs.numel(), directions, poses, dR, poses.shape[0],
+         directions.shape[0], grad_dR, grad_dT)
 
 
 class _PoseRays(torch.autograd.Function):

@@ -104,8 +104,7 @@ class _Bucket:
         from . import _lib
         t = self.view
         if self.wire is not None:
-            _lib.call("ncn_grad_pack_f16", _lib.ptr(self.view), _lib.I64(self.view.numel()), _lib.ptr(self.scale),
-                      _lib.I32(dist.get_world_size()), _lib.ptr(self.wire), _lib.stream())
+            _lib.call("ncn_grad_pack_f16", self.view, self.view.numel(), self.scale, dist.get_world_size(), self.wire)
             t = self.wire
         return dist.all_reduce(t, op=dist.ReduceOp.SUM, async_op=True)
 
@@ -113,8 +112,7 @@ class _Bucket:
         from . import _lib
         work.wait()
         if self.wire is not None:
-            _lib.call("ncn_grad_unpack_f16", _lib.ptr(self.wire), _lib.I64(self.view.numel()), _lib.ptr(self.scale),
-                      _lib.ptr(self.view), _lib.stream())
+            _lib.call("ncn_grad_unpack_f16", self.wire, self.view.numel(), self.scale, self.view)
 
 
 def reduce_gradients(model, graph=False):

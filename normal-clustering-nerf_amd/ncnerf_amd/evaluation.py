@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import I32, I64, U32, call, check_input, ptr, stream
+from ._lib import call, check_input
 
 MAX_K = 32                      # ncn_kmeans_train / ncn_kmeans_assign
 MAX_POINTS_PER_CENTROID = 256   # faiss ClusteringParameters default
@@ -49,7 +49,7 @@ def extract_normals_from_depth_batch(depth, ray_dirs_cc, poses):
     dirs = ray_dirs_cc.detach().float().contiguous()
     rot = poses.detach()[:, :3, :3].float().contiguous()
     normals = torch.empty(B, H, W, 3, dtype=torch.float32, device=depth.device)
-    call("ncn_depth_normals_image", ptr(depth), ptr(dirs), ptr(rot), I32(B), I32(H), I32(W), ptr(normals), stream())
+    call("ncn_depth_normals_image", depth, dirs, rot, B, H, W, normals)
     return normals
 
 
@@ -63,7 +63,7 @@ def kmeans_draws(nx, K, seed=1234):
     sub = np.empty(min(nx, K * MAX_POINTS_PER_CENTROID), np.int64)
     init = np.empty(K, np.int64)
     rows = np.empty(K, np.int64)
-    call("ncn_kmeans_draws", I64(nx), I32(K), U32(int(seed) & 0xFFFFFFFF), sub.ctypes.data_as(_lib.P),
+    call("ncn_kmeans_draws", nx, K, int(seed) & 0xFFFFFFFF, sub.ctypes.data_as(_lib.P),
          init.ctypes.data_as(_lib.P), rows.ctypes.data_as(_lib.P))
     return sub, init, rows
 
@@ -71,7 +71,7 @@ def kmeans_draws(nx, K, seed=1234):
 def kmeans_rand_floats(seed=SPLIT_SEED, n=N_RAND):
     """ncn_kmeans_rand_floats: faiss RandomGenerator(seed).rand_float() x n, f32 numpy (host only)."""
     out = np.empty(int(n), np.float32)
-    call("ncn_kmeans_rand_floats", U32(int(seed) & 0xFFFFFFFF), I32(int(n)), out.ctypes.data_as(_lib.P))
+    call("ncn_kmeans_rand_floats", int(seed) & 0xFFFFFFFF, int(n), out.ctypes.data_as(_lib.P))
     return out
 
 
@@ -99,11 +99,10 @@ def spherical_kmeans(X, K, niter, seed=1234):
     train = X[torch.from_numpy(sub).to(dev)].contiguous() if n > K * MAX_POINTS_PER_CENTROID else X
     init_dev = torch.from_numpy(rows).to(dev)
     cents = torch.empty(K, 3, dtype=torch.float32, device=dev)
-    call("ncn_kmeans_train", ptr(train), I32(train.shape[0]), I32(K), I32(int(niter)), ptr(init_dev),
-         ptr(_rand_floats_dev(dev)), ptr(cents), stream())
+    call("ncn_kmeans_train", train, train.shape[0], K, int(niter), init_dev, _rand_floats_dev(dev), cents)
     assign = torch.empty(n, dtype=torch.int32, device=dev)
     counts = torch.empty(K, dtype=torch.int64, device=dev)
-    call("ncn_kmeans_assign", ptr(X), I64(n), ptr(cents), I32(K), ptr(assign), ptr(counts), stream())
+    call("ncn_kmeans_assign", X, n, cents, K, assign, counts)
     return cents, assign, counts
 
 

@@ -29,7 +29,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib, vren
-from ._lib import F32, I32, I64, U32, call, check_input, ptr, stream
+from ._lib import call, check_input
 
 N_OUT = 11  # ncn_cluster_loss out_losses
 _WS = {}
@@ -42,7 +42,7 @@ def _cluster_workspace(dev, K):
     key = (str(dev), K)
     ws = _WS.get(key)
     if ws is None:
-        ws = torch.zeros(int(_lib.lib().ncn_cluster_workspace_words(I32(K))), dtype=torch.float32, device=dev)
+        ws = torch.zeros(int(_lib.lib().ncn_cluster_workspace_words(K)), dtype=torch.float32, device=dev)
         _WS[key] = ws
     return ws
 
@@ -56,11 +56,9 @@ def kmeans_plan(dev, n_tri, K, seed=1234):
     key = (str(dev), int(n_tri), int(K), int(seed))
     plan = _PLANS.get(key)
     if plan is None:
-        words = int(_lib.lib().ncn_kmeans_plan_words(I32(n_tri), I32(K)))
+        words = int(_lib.lib().ncn_kmeans_plan_words(n_tri, K))
         host = torch.zeros(words, dtype=torch.int32)
-        rc = _lib.lib().ncn_kmeans_plan_fill(I32(n_tri), I32(K), U32(seed), ptr(host))
-        if rc != 0:
-            raise _lib.NcnError("ncn_kmeans_plan_fill failed: " + _lib.lib().ncn_last_error().decode())
+        call("ncn_kmeans_plan_fill", n_tri, K, seed, host)
         plan = host.to(dev)
         _PLANS[key] = plan
     return plan
@@ -73,7 +71,7 @@ def check_cluster_status(dev=None):
     for (d, K), ws in _WS.items():
         if dev is not None and d != str(dev):
             continue
-        off = int(_lib.lib().ncn_cluster_status_offset(I32(K)))
+        off = int(_lib.lib().ncn_cluster_status_offset(K))
         if int(ws.view(torch.int32)[off].item()) != 0:
             raise _lib.NcnError(f"ncn_cluster_loss on {d} (K={K}): a grid barrier / Lloyd hand-off timed out "
                                 f"(its workgroups were not co-resident); cluster losses are invalid")
@@ -86,8 +84,7 @@ class _Normals(torch.autograd.Function):
     def forward(ctx, rays_o, rays_d, depth, x1, x2, x3):
         T = x1.shape[0]
         normals = torch.empty(T, 3, dtype=torch.float32, device=depth.device)
-        call("ncn_normals_fwd", ptr(rays_o), ptr(rays_d), ptr(depth), ptr(x1), ptr(x2), ptr(x3), I64(T), ptr(normals),
-             stream())
+        call("ncn_normals_fwd", rays_o, rays_d, depth, x1, x2, x3, T, normals)
         ctx.save_for_backward(rays_o, rays_d, depth, x1, x2, x3)
         return normals
 
@@ -100,13 +97,12 @@ class _Normals(torch.autograd.Function):
             # into them; with quirk q1, rays_o := rays_d, this is how the normal terms reach the poses)
             d_o, d_d = torch.zeros_like(rays_o), torch.zeros_like(rays_d)
             if dn is not None:
-                call("ncn_normals_bwd_rays", ptr(rays_o), ptr(rays_d), ptr(depth), ptr(x1), ptr(x2), ptr(x3),
-                     I64(x1.shape[0]), ptr(dn.contiguous().float()), None, ptr(ddepth), ptr(d_o), ptr(d_d), stream())
+                call("ncn_normals_bwd_rays", rays_o, rays_d, depth, x1, x2, x3,
+                     x1.shape[0], dn.contiguous().float(), None, ddepth, d_o, d_d)
             return (d_o if ctx.needs_input_grad[0] else None, d_d if ctx.needs_input_grad[1] else None, ddepth,
                     None, None, None)
         if dn is not None:
-            call("ncn_normals_bwd", ptr(rays_o), ptr(rays_d), ptr(depth), ptr(x1), ptr(x2), ptr(x3), I64(x1.shape[0]),
-                 ptr(dn.contiguous()), None, ptr(ddepth), stream())
+            call("ncn_normals_bwd", rays_o, rays_d, depth, x1, x2, x3, x1.shape[0], dn.contiguous(), None, ddepth)
         return None, None, ddepth, None, None, None
 
 
@@ -135,9 +131,8 @@ class _ClusterLoss(torch.autograd.Function):
         dn = torch.empty(3, T, 3, dtype=torch.float32, device=dev)
         ws = _cluster_workspace(dev, K)
         hw, w_dev = _split_weights(w)
-        call("ncn_cluster_loss", ptr(normals), I64(T), I32(K), I32(niter), ptr(kmeans_plan(dev, T, K, seed)), F32(t_sim), F32(hw[0]),
-             F32(hw[1]), F32(hw[2]), ptr(w_dev), ptr(None), F32(0.0), F32(1.0), ptr(None), ptr(out), ptr(labels),
-             ptr(cents), ptr(dn), ptr(ws), stream())
+        call("ncn_cluster_loss", normals, T, K, niter, kmeans_plan(dev, T, K, seed), t_sim, hw[0], hw[1], hw[2], w_dev,
+             None, 0.0, 1.0, None, out, labels, cents, dn, ws)
         ctx.save_for_backward(dn)
         terms = out[4:7].clone()
         ctx.mark_non_differentiable(labels, cents, out)
@@ -190,17 +185,15 @@ class _NormalsClusterLoss(torch.autograd.Function):
         T = x1.shape[0]
         dev = depth.device
         normals = torch.empty(T, 3, dtype=torch.float32, device=dev)
-        call("ncn_normals_fwd", ptr(rays_o), ptr(rays_d), ptr(depth), ptr(x1), ptr(x2), ptr(x3), I64(T), ptr(normals),
-             stream())
+        call("ncn_normals_fwd", rays_o, rays_d, depth, x1, x2, x3, T, normals)
         out = torch.empty(N_OUT, dtype=torch.float32, device=dev)
         labels = torch.empty(T, dtype=torch.int32, device=dev)
         cents = torch.empty(K, 3, dtype=torch.float32, device=dev)
         dn = torch.empty(3, T, 3, dtype=torch.float32, device=dev)
         ws = _cluster_workspace(dev, K)
         hw, w_dev = _split_weights(w)
-        call("ncn_cluster_loss", ptr(normals), I64(T), I32(K), I32(niter), ptr(kmeans_plan(dev, T, K, seed)), F32(t_sim), F32(hw[0]),
-             F32(hw[1]), F32(hw[2]), ptr(w_dev), ptr(None), F32(0.0), F32(1.0), ptr(None), ptr(out), ptr(labels),
-             ptr(cents), ptr(dn), ptr(ws), stream())
+        call("ncn_cluster_loss", normals, T, K, niter, kmeans_plan(dev, T, K, seed), t_sim, hw[0], hw[1], hw[2], w_dev,
+             None, 0.0, 1.0, None, out, labels, cents, dn, ws)
         ctx.save_for_backward(rays_o, rays_d, depth, x1, x2, x3, dn)
         terms = out[4:7].clone()
         ctx.mark_non_differentiable(normals, labels, cents, out)
@@ -212,8 +205,7 @@ class _NormalsClusterLoss(torch.autograd.Function):
         if g is None:
             return (None,) * 11
         ddepth = torch.zeros_like(depth)
-        call("ncn_normals_bwd", ptr(rays_o), ptr(rays_d), ptr(depth), ptr(x1), ptr(x2), ptr(x3), I64(x1.shape[0]),
-             ptr(dn), ptr(g.float().contiguous()), ptr(ddepth), stream())
+        call("ncn_normals_bwd", rays_o, rays_d, depth, x1, x2, x3, x1.shape[0], dn, g.float().contiguous(), ddepth)
         return None, None, ddepth, None, None, None, None, None, None, None, None
 
 
@@ -237,7 +229,7 @@ class _PhotoLoss(torch.autograd.Function):
     def forward(ctx, rgb, rgb_gt, opacity, w_op):
         R = rgb.shape[0]
         loss = torch.empty(4, dtype=torch.float32, device=rgb.device)
-        call("ncn_photo_loss_fwd", ptr(rgb), ptr(rgb_gt), ptr(opacity), I64(R), F32(w_op), ptr(loss), stream())
+        call("ncn_photo_loss_fwd", rgb, rgb_gt, opacity, R, w_op, loss)
         ctx.save_for_backward(rgb, rgb_gt, opacity, loss)
         ctx.w_op = w_op
         return loss[0], loss[1]
@@ -249,8 +241,7 @@ class _PhotoLoss(torch.autograd.Function):
         g = torch.stack([torch.zeros((), device=dev) if g_rgb is None else g_rgb.float(),
                          torch.zeros((), device=dev) if g_op is None else g_op.float()])
         drgb, dop = torch.empty_like(rgb), torch.empty_like(opacity)
-        call("ncn_photo_loss_bwd", ptr(rgb), ptr(rgb_gt), ptr(opacity), I64(rgb.shape[0]), F32(ctx.w_op), ptr(loss),
-             ptr(g), ptr(drgb), ptr(dop), stream())
+        call("ncn_photo_loss_bwd", rgb, rgb_gt, opacity, rgb.shape[0], ctx.w_op, loss, g, drgb, dop)
         return drgb, None, dop, None
 
 
@@ -284,18 +275,16 @@ class _NeRFLossFused(torch.autograd.Function):
         normals = torch.empty(T, 3, dtype=torch.float32, device=dev)
         cj = count_job  # (custom_functions.CountJob or None)
         tot = cj.total if cj is not None else None
-        call("ncn_photo_normals_count_fwd", ptr(rgb), ptr(rgb_gt), ptr(opacity), I64(R), F32(w_op), ptr(photo),
-             ptr(rays_o), ptr(rays_d), ptr(depth), ptr(x1), ptr(x2), ptr(x3), I64(T), ptr(normals), ptr(tot),
-             I64(tot.shape[0] if tot is not None else 0), ptr(cj.counter if cj else None),
-             ptr(cj.out if cj else None), ptr(cj.acc if cj else None), stream())
+        call("ncn_photo_normals_count_fwd", rgb, rgb_gt, opacity, R, w_op, photo, rays_o, rays_d, depth, x1, x2, x3, T,
+             normals, tot, tot.shape[0] if tot is not None else 0, cj.counter if cj else None, cj.out if cj else None,
+             cj.acc if cj else None)
         out = torch.empty(N_OUT, dtype=torch.float32, device=dev)
         labels = torch.empty(T, dtype=torch.int32, device=dev)
         cents = torch.empty(K, 3, dtype=torch.float32, device=dev)
         dn = torch.empty(3, T, 3, dtype=torch.float32, device=dev)
         ws = _cluster_workspace(dev, K)
-        call("ncn_cluster_loss", ptr(normals), I64(T), I32(K), I32(niter), ptr(kmeans_plan(dev, T, K, seed)), F32(t_sim), F32(w[0]),
-             F32(w[1]), F32(w[2]), ptr(None), ptr(step_dev), F32(sched[0]), F32(sched[1]), ptr(photo), ptr(out),
-             ptr(labels), ptr(cents), ptr(dn), ptr(ws), stream())
+        call("ncn_cluster_loss", normals, T, K, niter, kmeans_plan(dev, T, K, seed), t_sim, w[0], w[1], w[2], None,
+             step_dev, sched[0], sched[1], photo, out, labels, cents, dn, ws)
         ctx.save_for_backward(rgb, opacity, depth, rays_o, rays_d, rgb_gt, photo, dn)
         ctx.w_op = w_op
         ctx.set_materialize_grads(False)
@@ -314,9 +303,8 @@ class _NeRFLossFused(torch.autograd.Function):
         up_total = None if g_total is None else g_total.float().contiguous()
         R = rgb.shape[0]
         drgb, dop, ddepth = torch.empty_like(rgb), torch.empty_like(opacity), torch.empty_like(depth)
-        call("ncn_nerf_loss_bwd", ptr(rgb), ptr(rgb_gt), ptr(opacity), I64(R), F32(ctx.w_op), ptr(photo),
-             ptr(rays_o), ptr(rays_d), ptr(depth), ptr(dn), ptr(up_total), ptr(up_terms), ptr(drgb), ptr(dop),
-             ptr(ddepth), stream())
+        call("ncn_nerf_loss_bwd", rgb, rgb_gt, opacity, R, ctx.w_op, photo, rays_o, rays_d, depth, dn, up_total,
+             up_terms, drgb, dop, ddepth)
         return (drgb, dop, ddepth) + (None,) * 15
 
 
@@ -502,8 +490,7 @@ class NeRFMTLoss(nn.Module):
             return self._fused(pred_w_gt, target_gt, pred_unsup, dict(kwargs, count_job=pred_raw.get("_count_job")))
         job = pred_raw.get("_count_job")
         if job is not None:  # render left its sample count to the fused node, not used in this configuration
-            call("ncn_count_samples", ptr(job.total), I64(job.total.shape[0]), ptr(job.counter), ptr(job.out),
-                 ptr(job.acc), stream())
+            call("ncn_count_samples", job.total, job.total.shape[0], job.counter, job.out, job.acc)
         fuse_normals = (clustering and self.pred_norm_depth and unsup_start == 0 and self.norm_DEpth_L1_w == 0
                         and self.norm_DEpth_dot_w == 0 and not rays_grad)
         if self.pred_norm_depth and not fuse_normals:

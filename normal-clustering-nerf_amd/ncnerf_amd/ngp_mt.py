@@ -35,7 +35,7 @@ from einops import rearrange
 from torch import nn
 
 from . import _lib, vren
-from ._lib import I32, I64, F32, call, ptr, stream
+from ._lib import call
 
 L_LEVELS, F_PER_LEVEL, LOG2_T, N_MIN = 16, 2, 19, 16  # ngp_mt.py:40
 # tcnn's padded shapes (ngp_mt.py:83-113 through tcnn.Network): sigma_net W1 (64,32) W2 (16,64);
@@ -115,7 +115,7 @@ class _FieldFunction(torch.autograd.Function):
         need_d = d is not None and ctx.needs_input_grad[1]
         need_param = any(ctx.needs_input_grad[2:5])
         L = _lib.lib()
-        dE_ws = torch.empty(int(L.ncn_field_bwd_dE_floats(I64(n))), dtype=torch.float32, device=dev)
+        dE_ws = torch.empty(int(L.ncn_field_bwd_dE_floats(n)), dtype=torch.float32, device=dev)
         c = lambda t: None if t is None else t.contiguous().float()
         dsig, drgb = c(dL_dsigmas), c(dL_drgbs)
         scale = model._bwd_loss_scale()
@@ -123,43 +123,40 @@ class _FieldFunction(torch.autograd.Function):
         dL_dx = dL_dd = None
         if d is None:
             # density mode (no directions): the sigma part alone on a zero stash, dL/dh = TruncExp'(h0) dL/dsigma
-            nb = int(L.ncn_field_bwd_part_blocks(I64(n), I32(2)))
+            nb = int(L.ncn_field_bwd_part_blocks(n, 2))
             slab = torch.empty(nb * N_W, dtype=torch.float32, device=dev)
-            stash = torch.zeros(int(L.ncn_field_bwd_stash_floats(I64(n))), dtype=torch.float32, device=dev)
+            stash = torch.zeros(int(L.ncn_field_bwd_stash_floats(n)), dtype=torch.float32, device=dev)
             lmax = model._level_max()
             lmax.zero_()  # (the sigma part max-reduces into the rows the rgb part would have zeroed)
             dE_ws[:4].zero_()  # (header: no permuted positions in this workspace)
-            call("ncn_field_bwd_mlp_part", ptr(x), ptr(None), I64(n), ptr(n_dev), ptr(order), ptr(packed), I32(model._prec),
-                 ptr(enc), ptr(dsig), ptr(None), ptr(None), ptr(scale), I32(2), I32(0), ptr(slab), ptr(dE_ws), ptr(lmax),
-                 ptr(stash), stream())
+            call("ncn_field_bwd_mlp_part", x, None, n, n_dev, order, packed, model._prec, enc, dsig, None, None, scale,
+                 2, 0, slab, dE_ws, lmax, stash)
             if need_param:
                 model._scatter(x, n, n_dev, order, dE_ws, lmax, g_table)
-                call("ncn_field_reduce_wgrad_parts", ptr(slab), I32(nb), I32(0), ptr(g_w), stream())
+                call("ncn_field_reduce_wgrad_parts", slab, nb, 0, g_w)
         else:
-            nb = L.ncn_field_bwd_blocks(I64(n))
+            nb = L.ncn_field_bwd_blocks(n)
             slab = torch.empty(nb * N_W, dtype=torch.float32, device=dev)
             lmax = model._level_max()
             if need_param and not (need_x or need_d) and model.scatter_split is None:
-                call("ncn_field_bwd", ptr(x), ptr(d), I64(n), ptr(n_dev), ptr(order), model._levels_ptr, F32(model._xyz_min),
-                     F32(model._xyz_extent), ptr(packed), I32(model._prec), ptr(enc), ptr(dsig), ptr(drgb),
-                     ptr(scale), ptr(g_table), ptr(slab), ptr(dE_ws), ptr(lmax), stream())
+                call("ncn_field_bwd", x, d, n, n_dev, order, model._levels_ptr, model._xyz_min, model._xyz_extent,
+                     packed, model._prec, enc, dsig, drgb, scale, g_table, slab, dE_ws, lmax)
             else:
                 if need_d:
                     dL_dd = torch.empty(n, 3, dtype=torch.float32, device=dev)  # (the kernel zeroes rows >= *n_dev)
-                    call("ncn_field_bwd_mlp_din", ptr(x), ptr(d), I64(n), ptr(n_dev), ptr(order), ptr(packed), I32(model._prec),
-                         ptr(enc), ptr(dsig), ptr(drgb), ptr(scale), ptr(slab), ptr(dE_ws), ptr(lmax),
-                         ptr(model._flat[model._n_table:]), ptr(dL_dd), stream())
+                    call("ncn_field_bwd_mlp_din", x, d, n, n_dev, order, packed, model._prec, enc, dsig, drgb, scale,
+                         slab, dE_ws, lmax, model._flat[model._n_table:], dL_dd)
                 else:
-                    call("ncn_field_bwd_mlp", ptr(x), ptr(d), I64(n), ptr(n_dev), ptr(order), ptr(packed), I32(model._prec),
-                         ptr(enc), ptr(dsig), ptr(drgb), ptr(scale), ptr(slab), ptr(dE_ws), ptr(lmax), stream())
+                    call("ncn_field_bwd_mlp", x, d, n, n_dev, order, packed, model._prec,
+                         enc, dsig, drgb, scale, slab, dE_ws, lmax)
                 if need_param:
                     model._scatter(x, n, n_dev, order, dE_ws, lmax, g_table)
             if need_param:
-                call("ncn_field_reduce_wgrad", ptr(slab), I32(nb), ptr(g_w), stream())
+                call("ncn_field_reduce_wgrad", slab, nb, g_w)
         if need_x:
             dL_dx = torch.empty(n, 3, dtype=torch.float32, device=dev)  # (the kernel zeroes rows >= *n_dev)
-            call("ncn_field_bwd_dx", ptr(x), I64(n), ptr(n_dev), ptr(order), ptr(table), model._levels_ptr,
-                 F32(model._xyz_min), F32(model._xyz_extent), ptr(dE_ws), ptr(dL_dx), stream())
+            call("ncn_field_bwd_dx", x, n, n_dev, order, table, model._levels_ptr,
+                 model._xyz_min, model._xyz_extent, dE_ws, dL_dx)
         return dL_dx, dL_dd, None, None, None, None, None, None
 
 
@@ -311,9 +308,8 @@ class NGPMT(nn.Module):
         if not entries:
             raise RuntimeError("run_deferred_scatter: no deferred scatter (scatter_split unset or no backward yet)")
         for x, n, n_dev, order, dE_ws, lmax, g_table in entries:
-            call("ncn_field_scatter", ptr(x), I64(n), ptr(n_dev), ptr(order), self._levels_ptr, F32(self._xyz_min),
-                 F32(self._xyz_extent), ptr(dE_ws), ptr(lmax), I32(0), I32(self.scatter_split), I32(max_blocks),
-                 ptr(g_table), stream())
+            call("ncn_field_scatter", x, n, n_dev, order, self._levels_ptr, self._xyz_min, self._xyz_extent, dE_ws,
+                 lmax, 0, self.scatter_split, max_blocks, g_table)
         if not graph:
             self._deferred = []
 
@@ -346,7 +342,7 @@ class NGPMT(nn.Module):
         inv = getattr(self, "_pack_inv", None)
         if inv is None or inv.device != self._flat.device:
             src = torch.empty(N_PACKED_HALVES, dtype=torch.int32, device=self._flat.device)
-            call("ncn_field_pack_map", ptr(src), stream())
+            call("ncn_field_pack_map", src)
             s = src.cpu().numpy()
             table = np.full((N_W, 2), -1, np.int32)
             fill = np.zeros(N_W, np.int64)
@@ -360,7 +356,7 @@ class NGPMT(nn.Module):
     def _pack_weights(self):
         if self._packed is None or self._packed.device != self._flat.device:
             self._packed = torch.empty(N_PACKED_HALVES, dtype=torch.float16, device=self._flat.device)
-        call("ncn_field_pack_weights", ptr(self._flat[self._n_table:]), ptr(self._packed), I32(self._prec), stream())
+        call("ncn_field_pack_weights", self._flat[self._n_table:], self._packed, self._prec)
         return self._packed
 
     # -- field -----------------------------------------------------------------------------------
@@ -381,11 +377,9 @@ class NGPMT(nn.Module):
             # processing order: Morton-sorted windows of 4096 samples (ncn_field_sort_windows); the
             # encoding cache and the backward's dE are kept in it, the outputs stay in sample order
             order = torch.empty(n, dtype=torch.int32, device=dev)
-            call("ncn_field_sort_windows", ptr(x), I64(n), ptr(n_dev), F32(self._xyz_min), F32(self._xyz_extent),
-                 ptr(order), stream())
-        call("ncn_field_fwd", ptr(x), ptr(d) if mode == 0 else ptr(None), I64(n), ptr(n_dev), ptr(order),
-             ptr(self.xyz_encoder.params), self._levels_ptr, F32(self._xyz_min), F32(self._xyz_extent), ptr(packed), I32(self._prec), I32(mode),
-             ptr(sigmas), ptr(rgbs) if mode == 0 else ptr(None), ptr(enc), stream())
+            call("ncn_field_sort_windows", x, n, n_dev, self._xyz_min, self._xyz_extent, order)
+        call("ncn_field_fwd", x, d if mode == 0 else None, n, n_dev, order, self.xyz_encoder.params, self._levels_ptr,
+             self._xyz_min, self._xyz_extent, packed, self._prec, mode, sigmas, rgbs if mode == 0 else None, enc)
         return sigmas, rgbs, enc, packed, order
 
     def _scatter(self, x, n, n_dev, order, dE_ws, lmax, g_table, wgrad=None):
@@ -397,9 +391,8 @@ class NGPMT(nn.Module):
         split = self.scatter_split
         lo = 0 if split is None else split
         slab, nb_s, nb_r, g_w = wgrad if wgrad is not None else (None, 0, 0, None)
-        call("ncn_field_scatter_wgrad", ptr(x), I64(n), ptr(n_dev), ptr(order), self._levels_ptr, F32(self._xyz_min),
-             F32(self._xyz_extent), ptr(dE_ws), ptr(lmax), I32(lo), I32(16), I32(0), ptr(g_table), ptr(slab),
-             I32(nb_s), I32(nb_r), ptr(g_w), stream())
+        call("ncn_field_scatter_wgrad", x, n, n_dev, order, self._levels_ptr, self._xyz_min, self._xyz_extent, dE_ws,
+             lmax, lo, 16, 0, g_table, slab, nb_s, nb_r, g_w)
         if split is not None:
             # (a list: a step with two field backwards — e.g. density() with grad and forward() —
             # leaves two pending coarse-level scatters, both run by run_deferred_scatter)
@@ -545,10 +538,9 @@ class NGPMT(nn.Module):
             cc = cnt[c] if cnt is not None else None
 
             def sample():
-                call("ncn_grid_sample", ptr(dgc), I64(N), I32(G), F32(s - half_grid_size), F32(half_grid_size),
-                     F32(density_threshold), I64(N // 4), I32(1 if warmup else 0),
-                     _lib.U64((seed + 0x9E3779B97F4A7C15 * c) % 2 ** 64), F32(decay), ptr(cc), ptr(ws["xyzs"]),
-                     ptr(ws["idx"]), ptr(n_list), ptr(ws["work"]), stream())
+                call("ncn_grid_sample", dgc, N, G, s - half_grid_size, half_grid_size, density_threshold, N // 4,
+                     1 if warmup else 0, (seed + 0x9E3779B97F4A7C15 * c) % 2 ** 64, decay, cc, ws["xyzs"], ws["idx"],
+                     n_list, ws["work"])
 
             if c == 0 and beside is not None:
                 cur = torch.cuda.current_stream(dg.device)
@@ -564,14 +556,11 @@ class NGPMT(nn.Module):
                 packed = self._take_packed()  # (after `beside`: the optimizer may have refreshed the fragments)
             # density pass, mode 2: the hash-grid encoding split by level over the XCDs into the
             # scratch ws["enc"] (each L2 serves two levels' tables), then sigma_net from it
-            call("ncn_field_fwd", ptr(ws["xyzs"]), ptr(None), I64(N), ptr(n_list), ptr(None), ptr(table), self._levels_ptr,
-                 F32(self._xyz_min), F32(self._xyz_extent), ptr(packed), I32(self._prec), I32(2), ptr(ws["sigmas"]), ptr(None),
-                 ptr(ws["enc"]), stream())
-            call("ncn_grid_apply", ptr(dgc), ptr(ws["idx"]), ptr(ws["sigmas"]), ptr(n_list), I64(N), F32(decay),
-                 ptr(cc), stream())
+            call("ncn_field_fwd", ws["xyzs"], None, N, n_list, None, table, self._levels_ptr, self._xyz_min,
+                 self._xyz_extent, packed, self._prec, 2, ws["sigmas"], None, ws["enc"])
+            call("ncn_grid_apply", dgc, ws["idx"], ws["sigmas"], n_list, N, decay, cc)
         thr_out = ws["scal"][1:2].view(torch.float32)
-        call("ncn_grid_packbits", ptr(dg), I64(C * N), _lib.F64(density_threshold), ptr(self.density_bitfield),
-             ptr(thr_out), ptr(ws["work"]), stream())
+        call("ncn_grid_packbits", dg, C * N, density_threshold, self.density_bitfield, thr_out, ws["work"])
 
 
 def register_grid_buffers(model):

@@ -13,7 +13,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import F32, I32, I64, call, ptr, stream
+from ._lib import call
 
 
 class FlatAdam:
@@ -63,19 +63,17 @@ class FlatAdam:
         p = self.model.flat_params()
         g = self.model.flat_grad()
         b1, b2 = self.betas
-        args = [ptr(p), ptr(g), ptr(self.m), ptr(self.v), I64(p.numel()), I64(self.n_table), F32(grad_scale),
-                F32(self.max_norm), F32(self.lr), _lib.F64(b1), _lib.F64(b2), F32(self.eps), F32(self.wd[0]),
-                F32(self.wd[1]), ptr(self.lr_dev), ptr(self.step_dev), ptr(self.work),
-                I32(1 if self.zero_grad_on_step else 0), ptr(getattr(self.model, "amp_state", None)),
-                ptr(self.gate if gated else None)]
+        args = [p, g, self.m, self.v, p.numel(), self.n_table, grad_scale, self.max_norm, self.lr, b1, b2, self.eps,
+                self.wd[0], self.wd[1], self.lr_dev, self.step_dev, self.work, 1 if self.zero_grad_on_step else 0,
+                getattr(self.model, "amp_state", None), self.gate if gated else None]
         if self.pack_fused:
             # the field's packed MLP fragments refreshed by the Adam pass itself (ncn_adam_step_packed):
             # afterwards they match the parameters whether the step applied or was skipped
             inv, off, packed, prec = self.model.pack_target()
-            call("ncn_adam_step_packed", *args, ptr(inv), I64(off), ptr(packed), I32(prec), stream())
+            call("ncn_adam_step_packed", *args, inv, off, packed, prec)
             self.model._packed_fresh = True
         else:
-            call("ncn_adam_step", *args, stream())
+            call("ncn_adam_step", *args)
 
     def state_tensors(self):
         """Every tensor the step mutates (parameters, moments, device counters)."""

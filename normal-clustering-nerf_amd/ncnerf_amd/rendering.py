@@ -119,14 +119,10 @@ def render_rays_test(model, rays_o, rays_d, hits_t, **kwargs):
             dir_c = torch.empty(cap, 3, dtype=torch.float32, device=device)
             offs = torch.empty(N_alive, dtype=torch.int32, device=device)
             cnt = torch.empty(1, dtype=torch.int32, device=device)
-            _lib.call("ncn_test_compact", _lib.ptr(xyzs), _lib.ptr(dirs), _lib.ptr(N_eff_samples), _lib.I64(N_alive),
-                      _lib.I32(N_samples), _lib.ptr(offs), _lib.ptr(xyz_c), _lib.ptr(dir_c), _lib.ptr(cnt),
-                      _lib.stream())
+            _lib.call("ncn_test_compact", xyzs, dirs, N_eff_samples, N_alive, N_samples, offs, xyz_c, dir_c, cnt)
             sig, rgb = model._field_fwd(xyz_c, dir_c, cnt, 0, False)[:2]
-            _lib.call("ncn_composite_test_fw_compact", _lib.ptr(sig), _lib.ptr(rgb), _lib.ptr(offs), _lib.ptr(deltas),
-                      _lib.ptr(ts), _lib.ptr(alive_indices), _lib.I64(N_alive), _lib.I32(N_samples), _lib.I32(3),
-                      _lib.F32(float(kwargs.get("T_threshold", 1e-4))), _lib.ptr(N_eff_samples), _lib.ptr(opacity),
-                      _lib.ptr(depth), _lib.ptr(rend), _lib.stream())
+            _lib.call("ncn_composite_test_fw_compact", sig, rgb, offs, deltas, ts, alive_indices, N_alive, N_samples, 3,
+                      float(kwargs.get("T_threshold", 1e-4)), N_eff_samples, opacity, depth, rend)
             if stats is not None:
                 t0 = time.perf_counter()
             alive_indices = alive_indices[alive_indices >= 0]  # (host sync: the compaction's size)
@@ -189,7 +185,7 @@ def _test_loop_device(model, rays_o, rays_d, hits_t0, alive, exp_step_factor, ma
     done flag (iterations past the end launch empty).  Same outputs as the host-driven loop bit for
     bit: every ray's march and composite are independent of its position in the alive list.  Returns
     total_samples (device int64)."""
-    from ._lib import F32, I32, I64, call, ptr, stream
+    from ._lib import call
     R, dev = rays_o.shape[0], rays_o.device
     cap = R * min_samples
     f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
@@ -211,18 +207,16 @@ def _test_loop_device(model, rays_o, rays_d, hits_t0, alive, exp_step_factor, ma
     while it <= max_samples:  # (every iteration adds >= 1 to samples: at most max_samples run)
         for _ in range(TEST_LOOP_CHECK):
             a, b = bufs[it % 2], bufs[(it + 1) % 2]
-            call("ncn_test_loop_march", ptr(rays_o), ptr(rays_d), ptr(hits_t0), ptr(a), I64(R), ptr(model.density_bitfield),
-                 I32(int(model.cascades)), F32(float(model.scale)), F32(float(exp_step_factor)), I32(int(model.grid_size)),
-                 I32(int(max_samples)), ptr(ctrl), ptr(xyzs), ptr(dirs), ptr(deltas), ptr(ts), ptr(n_eff), stream())
-            call("ncn_test_loop_index", ptr(n_eff), I64(R), ptr(ctrl), ptr(idx), stream())
+            call("ncn_test_loop_march", rays_o, rays_d, hits_t0, a, R, model.density_bitfield,
+                 int(model.cascades), float(model.scale), float(exp_step_factor), int(model.grid_size),
+                 int(max_samples), ctrl, xyzs, dirs, deltas, ts, n_eff)
+            call("ncn_test_loop_index", n_eff, R, ctrl, idx)
             # the field on exactly the valid slots (order = their indices, count on the device)
-            call("ncn_field_fwd", ptr(xyzs), ptr(dirs), I64(cap), ptr(count), ptr(idx), ptr(model.xyz_encoder.params),
-                 model._levels_ptr, F32(model._xyz_min), F32(model._xyz_extent), ptr(packed), I32(model._prec), I32(0),
-                 ptr(sig), ptr(rgb), ptr(None), stream())
-            call("ncn_test_loop_composite", ptr(sig), ptr(rgb), ptr(None), ptr(deltas), ptr(ts), ptr(a), I64(R),
-                 ptr(ctrl), I32(3), F32(T_threshold), ptr(n_eff), ptr(opacity), ptr(depth), ptr(rend), stream())
-            call("ncn_test_loop_next", ptr(a), ptr(b), I64(R), ptr(ctrl), ptr(total), I32(R), I32(int(max_samples)),
-                 I32(int(min_samples)), stream())
+            call("ncn_field_fwd", xyzs, dirs, cap, count, idx, model.xyz_encoder.params, model._levels_ptr,
+                 model._xyz_min, model._xyz_extent, packed, model._prec, 0, sig, rgb, None)
+            call("ncn_test_loop_composite", sig, rgb, None, deltas, ts, a, R,
+                 ctrl, 3, T_threshold, n_eff, opacity, depth, rend)
+            call("ncn_test_loop_next", a, b, R, ctrl, total, R, int(max_samples), int(min_samples))
             it += 1
         t0 = time.perf_counter()
         done = bool(ctrl[3].item())  # (host sync)
@@ -355,7 +349,7 @@ def march_train_fused(model, rays_o, rays_d, near_distance, max_samples, noise=N
     rng = (seed, int64 device counter) draws it on the device (graph replays advance the counter),
     else torch.rand_like as the reference (custom_functions.py:83).  out: a previous result (or
     march_buffers()) whose tensors are overwritten in place; its '_slab' scratch is reused."""
-    from ._lib import F32, I32, I64, U64, call, check_input, lib, ptr, stream
+    from ._lib import call, check_input, lib
     rays_o = rays_o.contiguous().float()
     rays_d = rays_d.contiguous().float()
     check_input(rays_o, "rays_o")
@@ -376,24 +370,23 @@ def march_train_fused(model, rays_o, rays_d, near_distance, max_samples, noise=N
         raise RuntimeError("march_train_fused: out= buffers are sized for another batch")
     slab_xyz, slab_t, slab_dt, ws = out["_slab"]
     c, h = model._aabb
-    call("ncn_march_train_fused", ptr(rays_o), ptr(rays_d), I64(R), F32(c[0]), F32(c[1]), F32(c[2]), F32(h[0]),
-         F32(h[1]), F32(h[2]), F32(near_distance), ptr(noise), U64(int(seed) % 2 ** 64), ptr(ctr),
-         ptr(model.density_bitfield), I32(int(model.cascades)), F32(float(model.scale)), I32(int(model.grid_size)),
-         I32(ms), ptr(slab_xyz), ptr(slab_t), ptr(slab_dt), ptr(ws), ptr(out["rays_a"]), ptr(out["xyzs"]),
-         ptr(out["dirs"]), ptr(out["deltas"]), ptr(out["ts"]), ptr(out["counter"]), stream())
+    call("ncn_march_train_fused", rays_o, rays_d, R, c[0], c[1], c[2], h[0], h[1], h[2], near_distance, noise,
+         int(seed) % 2 ** 64, ctr, model.density_bitfield, int(model.cascades), float(model.scale),
+         int(model.grid_size), ms, slab_xyz, slab_t, slab_dt, ws, out["rays_a"], out["xyzs"], out["dirs"],
+         out["deltas"], out["ts"], out["counter"])
     return out
 
 
 def march_buffers(R, max_samples, device, share_scratch=None):
     """Output + scratch buffers of march_train_fused for R rays (capacity R*max_samples samples);
     share_scratch: another march_buffers() whose scratch (slabs, work) is reused (never concurrently)."""
-    from ._lib import I64, lib
+    from ._lib import lib
     cap = R * int(max_samples)
     f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=device)
     if share_scratch is not None:
         scratch = share_scratch["_slab"]
     else:
-        ws = torch.empty((int(lib().ncn_march_train_fused_work_bytes(I64(R))) + 3) // 4, dtype=torch.int32,
+        ws = torch.empty((int(lib().ncn_march_train_fused_work_bytes(R)) + 3) // 4, dtype=torch.int32,
                          device=device)
         scratch = (f(cap * 3), f(cap), f(cap), ws)
     out = {"rays_a": torch.empty(R, 3, dtype=torch.int64, device=device), "xyzs": f(cap, 3), "dirs": f(cap, 3),

@@ -35,7 +35,7 @@ import ctypes
 import torch
 
 from . import _lib, vren
-from ._lib import F32, I32, I64, call, ptr, stream
+from ._lib import call
 from .losses import N_OUT, _cluster_workspace, _standard_patch_offsets, kmeans_plan
 from .ngp_mt import N_W
 from .rendering import march_train_fused
@@ -59,7 +59,7 @@ def device_rgb_blocks():
     cus x per_cu)."""
     cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
     cap = ctypes.c_int(0)
-    _lib.lib().ncn_cluster_coresidency(I32(K_CLUSTERS), I32(0), ctypes.byref(cap))  # rc != 0 leaves cap < 16
+    _lib.lib().ncn_cluster_coresidency(K_CLUSTERS, 0, ctypes.byref(cap))  # rc != 0 leaves cap < 16
     return split_rgb_blocks(cus, cap.value // max(cus, 1))
 
 
@@ -102,7 +102,7 @@ class SplitStep:
         if self.rgb_blocks < 1:
             raise _lib.NcnError("SplitStep: the device cannot hold the clustering's workgroups beside an rgb pass")
         cap = ctypes.c_int(0)
-        call("ncn_cluster_coresidency", I32(K_CLUSTERS), I32(self.rgb_blocks), ctypes.byref(cap))
+        call("ncn_cluster_coresidency", K_CLUSTERS, self.rgb_blocks, ctypes.byref(cap))
         self.cluster_capacity = cap.value
 
     def _triangles(self, R, dev):
@@ -142,9 +142,8 @@ class SplitStep:
         acc = kw.get("count_acc")
         rgb_gt = batch["rgb"].contiguous().float()
         # (the normals use results["rays_o"] = rays_d, rendering.py:227 quirk q1)
-        call("ncn_photo_normals_count_fwd", ptr(rgb), ptr(rgb_gt), ptr(opacity), I64(R), F32(L.opacity_w), ptr(photo),
-             ptr(rays_d), ptr(rays_d), ptr(depth), ptr(x1), ptr(x2), ptr(x3), I64(T), ptr(normals), ptr(total_s),
-             I64(R), ptr(n_dev if acc is not None else None), ptr(cnt), ptr(acc), stream())
+        call("ncn_photo_normals_count_fwd", rgb, rgb_gt, opacity, R, L.opacity_w, photo, rays_d, rays_d, depth, x1, x2,
+             x3, T, normals, total_s, R, n_dev if acc is not None else None, cnt, acc)
         out = torch.empty(N_OUT, dtype=torch.float32, device=dev)
         labels = torch.empty(T, dtype=torch.int32, device=dev)
         cents = torch.empty(K_CLUSTERS, 3, dtype=torch.float32, device=dev)
@@ -154,44 +153,38 @@ class SplitStep:
         w = (L.norm_D_C_ort_dot_w, L.norm_D_C_centr_dot_w, L.norm_D_C_centr_L1_w)
         one = tr._unit(dev)
         lib = _lib.lib()
-        nb = (min(self.rgb_blocks, int(lib.ncn_field_bwd_part_blocks(I64(n), I32(1)))),
-              int(lib.ncn_field_bwd_part_blocks(I64(n), I32(2))))  # (the sigma pass: two workgroups per CU)
+        nb = (min(self.rgb_blocks, int(lib.ncn_field_bwd_part_blocks(n, 1))),
+              int(lib.ncn_field_bwd_part_blocks(n, 2)))  # (the sigma pass: two workgroups per CU)
         drgb, dop, ddepth = torch.empty_like(rgb), torch.empty_like(opacity), torch.empty_like(depth)
         slab = torch.empty(max(nb) * N_W, dtype=torch.float32, device=dev)
-        dE_ws = torch.empty(int(lib.ncn_field_bwd_dE_floats(I64(n))), dtype=torch.float32, device=dev)
-        stash = torch.empty(int(lib.ncn_field_bwd_stash_floats(I64(n))), dtype=torch.float32, device=dev)
+        dE_ws = torch.empty(int(lib.ncn_field_bwd_dE_floats(n)), dtype=torch.float32, device=dev)
+        stash = torch.empty(int(lib.ncn_field_bwd_stash_floats(n)), dtype=torch.float32, device=dev)
         lmax = m._level_max()
         scale = m._bwd_loss_scale()
         g_table, g_w = m._grad_views()
 
         def mlp_part(part, dsig, drw):
-            call("ncn_field_bwd_mlp_part", ptr(xyzs), ptr(dirs), I64(n), ptr(n_dev), ptr(order), ptr(packed), I32(m._prec),
-                 ptr(enc), ptr(dsig), ptr(None), ptr(drw), ptr(scale), I32(part), I32(nb[part - 1]), ptr(slab),
-                 ptr(dE_ws),
-                 ptr(lmax), ptr(stash), stream())
+            call("ncn_field_bwd_mlp_part", xyzs, dirs, n, n_dev, order, packed, m._prec, enc, dsig, None, drw, scale,
+                 part, nb[part - 1], slab, dE_ws, lmax, stash)
 
         # the photometric backward on a side stream (its first launch waits for the fork; the
         # clustering, issued first on this stream, takes its CUs before the rgb pass fills the rest)
         cur = torch.cuda.current_stream(dev)
         side = tr._side_stream()
         side.wait_stream(cur)
-        call("ncn_cluster_loss", ptr(normals), I64(T), I32(K_CLUSTERS), I32(K_ITERS), ptr(plan),
-             F32(1.0 - L.norm_CAN_tres), F32(w[0]), F32(w[1]), F32(w[2]), ptr(None), ptr(step_dev),
-             F32(float(L.can_sched_start)), F32(float(L._grow)), ptr(photo), ptr(out), ptr(labels), ptr(cents),
-             ptr(dn), ptr(cws), stream())
+        call("ncn_cluster_loss", normals, T, K_CLUSTERS, K_ITERS, plan, 1.0 - L.norm_CAN_tres, w[0], w[1], w[2], None,
+             step_dev, float(L.can_sched_start), float(L._grow), photo, out, labels, cents, dn, cws)
         with torch.cuda.stream(side):
             # ---- photometric backward: loss -> composite -> field MLP (rgb part) ----
-            call("ncn_nerf_loss_bwd", ptr(rgb), ptr(rgb_gt), ptr(opacity), I64(R), F32(L.opacity_w), ptr(photo),
-                 ptr(rays_d), ptr(rays_d), ptr(depth), ptr(None), ptr(one), ptr(None), ptr(drgb), ptr(dop),
-                 ptr(None), stream())
+            call("ncn_nerf_loss_bwd", rgb, rgb_gt, opacity, R, L.opacity_w, photo, rays_d, rays_d, depth, None, one,
+                 None, drgb, dop, None)
             # dL/draws = w * dL/drgb: the photometric gradient alone, bit for bit the joint backward's
             _, draws = vren.composite_train_multi_bw(dop, None, drgb, None, sigmas, rgbs, ws, deltas, ts, rays_a,
                                                      opacity, depth, rend, T_thr, bg=1.0)
             mlp_part(1, None, draws)
         # ---- clustering backward: loss (depth) -> composite (all terms) -> field MLP (sigma part) ----
-        call("ncn_nerf_loss_bwd", ptr(rgb), ptr(rgb_gt), ptr(opacity), I64(R), F32(L.opacity_w), ptr(photo),
-             ptr(rays_d), ptr(rays_d), ptr(depth), ptr(dn), ptr(one), ptr(None), ptr(None), ptr(None), ptr(ddepth),
-             stream())
+        call("ncn_nerf_loss_bwd", rgb, rgb_gt, opacity, R, L.opacity_w, photo,
+             rays_d, rays_d, depth, dn, one, None, None, None, ddepth)
         cur.wait_stream(side)
         # dL/dsigma from all three upstream terms in one expression, as the autograd step's backward
         dsig, _ = vren.composite_train_multi_bw(dop, ddepth, drgb, None, sigmas, rgbs, ws, deltas, ts, rays_a,

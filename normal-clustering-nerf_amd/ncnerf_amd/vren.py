@@ -17,7 +17,7 @@ Deliberate differences (DESIGN.md "Parity contract"):
 import torch
 
 from . import _lib
-from ._lib import F32, I32, I64, call, check_dtype, check_input, ptr, stream
+from ._lib import call, check_dtype, check_input
 
 
 def ray_aabb_intersect(rays_o, rays_d, centers, half_sizes, max_hits, near_distance=None):
@@ -32,11 +32,10 @@ def ray_aabb_intersect(rays_o, rays_d, centers, half_sizes, max_hits, near_dista
     hits_t = torch.empty(R, max_hits, 2, dtype=torch.float32, device=dev)
     hits_idx = torch.empty(R, max_hits, dtype=torch.int64, device=dev)
     if near_distance is None:
-        call("ncn_ray_aabb_intersect", ptr(rays_o), ptr(rays_d), I64(R), ptr(centers), ptr(half_sizes), I64(V),
-             I32(max_hits), ptr(hit_cnt), ptr(hits_t), ptr(hits_idx), stream())
+        call("ncn_ray_aabb_intersect", rays_o, rays_d, R, centers, half_sizes, V, max_hits, hit_cnt, hits_t, hits_idx)
     else:
-        call("ncn_ray_aabb_intersect_near", ptr(rays_o), ptr(rays_d), I64(R), ptr(centers), ptr(half_sizes), I64(V),
-             I32(max_hits), F32(float(near_distance)), ptr(hit_cnt), ptr(hits_t), ptr(hits_idx), stream())
+        call("ncn_ray_aabb_intersect_near", rays_o, rays_d, R, centers, half_sizes, V,
+             max_hits, float(near_distance), hit_cnt, hits_t, hits_idx)
     return [hit_cnt, hits_t, hits_idx]
 
 
@@ -45,7 +44,7 @@ def morton3D(coords):
     check_input(coords, "coords")
     check_dtype(coords, torch.int32, "coords")
     out = torch.empty(coords.shape[0], dtype=torch.int32, device=coords.device)
-    call("ncn_morton3D", ptr(coords), I64(coords.shape[0]), ptr(out), stream())
+    call("ncn_morton3D", coords, coords.shape[0], out)
     return out
 
 
@@ -54,7 +53,7 @@ def morton3D_invert(indices):
     check_input(indices, "indices")
     check_dtype(indices, torch.int32, "indices")
     out = torch.empty(indices.shape[0], 3, dtype=torch.int32, device=indices.device)
-    call("ncn_morton3D_invert", ptr(indices), I64(indices.shape[0]), ptr(out), stream())
+    call("ncn_morton3D_invert", indices, indices.shape[0], out)
     return out
 
 
@@ -66,7 +65,7 @@ def packbits(density_grid, density_threshold, density_bitfield):
     n = density_bitfield.shape[0]
     if density_grid.numel() < 8 * n:
         raise RuntimeError("density_grid has fewer than 8*len(density_bitfield) cells")
-    call("ncn_packbits", ptr(density_grid), I64(n), F32(float(density_threshold)), ptr(density_bitfield), stream())
+    call("ncn_packbits", density_grid, n, float(density_threshold), density_bitfield)
 
 
 def raymarching_train(rays_o, rays_d, hits_t, density_bitfield, cascades, scale, exp_step_factor, noise,
@@ -84,7 +83,6 @@ def raymarching_train(rays_o, rays_d, hits_t, density_bitfield, cascades, scale,
     R = rays_o.shape[0]
     dev = rays_o.device
     ms = int(max_samples)
-    s = stream()
     counts = torch.empty(R, dtype=torch.int32, device=dev)
     slab_xyz = torch.empty(R * ms * 3, dtype=torch.float32, device=dev)
     slab_t = torch.empty(R * ms, dtype=torch.float32, device=dev)
@@ -93,10 +91,9 @@ def raymarching_train(rays_o, rays_d, hits_t, density_bitfield, cascades, scale,
         raise ValueError("out= needs static_capacity=True")
     rays_a = out[0] if out is not None else torch.empty(R, 3, dtype=torch.int64, device=dev)
     counter = out[5] if out is not None else torch.empty(2, dtype=torch.int32, device=dev)
-    call("ncn_march_train_walk", ptr(rays_o), ptr(rays_d), ptr(hits_t), ptr(noise), I64(R), ptr(density_bitfield),
-         I32(int(cascades)), F32(float(scale)), F32(float(exp_step_factor)), I32(int(grid_size)), I32(ms),
-         ptr(counts), ptr(slab_xyz), ptr(slab_t), ptr(slab_dt), s)
-    call("ncn_march_train_scan", ptr(counts), I64(R), ptr(rays_a), ptr(counter), s)
+    call("ncn_march_train_walk", rays_o, rays_d, hits_t, noise, R, density_bitfield, int(cascades), float(scale),
+         float(exp_step_factor), int(grid_size), ms, counts, slab_xyz, slab_t, slab_dt)
+    call("ncn_march_train_scan", counts, R, rays_a, counter)
     S = R * ms if static_capacity else int(counter[0].item())
     if out is not None:
         xyzs, dirs, deltas, ts = out[1:5]
@@ -107,8 +104,7 @@ def raymarching_train(rays_o, rays_d, hits_t, density_bitfield, cascades, scale,
         dirs = torch.empty(S, 3, dtype=torch.float32, device=dev)
         deltas = torch.empty(S, dtype=torch.float32, device=dev)
         ts = torch.empty(S, dtype=torch.float32, device=dev)
-    call("ncn_march_train_pack", ptr(rays_d), ptr(rays_a), I64(R), I32(ms), ptr(slab_xyz), ptr(slab_t),
-         ptr(slab_dt), ptr(xyzs), ptr(dirs), ptr(deltas), ptr(ts), s)
+    call("ncn_march_train_pack", rays_d, rays_a, R, ms, slab_xyz, slab_t, slab_dt, xyzs, dirs, deltas, ts)
     return [rays_a, xyzs, dirs, deltas, ts, counter]
 
 
@@ -139,7 +135,7 @@ def raymarching_train_backward(dL_dxyzs, dL_ddirs, ts, rays_a):
         hi = max(hi_start, hi_end)
         if lo < 0 or hi > S:
             raise RuntimeError(f"rays_a segments reach outside the {S} samples ([{lo}, {hi}))")
-    call("ncn_segment_csr", ptr(dL_dxyzs), ptr(dL_ddirs), ptr(ts), ptr(rays_a), I64(R), ptr(d_o), ptr(d_d), stream())
+    call("ncn_segment_csr", dL_dxyzs, dL_ddirs, ts, rays_a, R, d_o, d_d)
     return [d_o, d_d]
 
 
@@ -157,9 +153,8 @@ def raymarching_test(rays_o, rays_d, hits_t, alive_indices, density_bitfield, ca
     deltas = torch.empty(A, N, dtype=torch.float32, device=dev)
     ts = torch.empty(A, N, dtype=torch.float32, device=dev)
     n_eff = torch.empty(A, dtype=torch.int32, device=dev)
-    call("ncn_march_test", ptr(rays_o), ptr(rays_d), ptr(hits_t), ptr(alive_indices), I64(A), ptr(density_bitfield),
-         I32(int(cascades)), F32(float(scale)), F32(float(exp_step_factor)), I32(int(grid_size)),
-         I32(int(max_samples)), I32(N), ptr(xyzs), ptr(dirs), ptr(deltas), ptr(ts), ptr(n_eff), stream())
+    call("ncn_march_test", rays_o, rays_d, hits_t, alive_indices, A, density_bitfield, int(cascades), float(scale),
+         float(exp_step_factor), int(grid_size), int(max_samples), N, xyzs, dirs, deltas, ts, n_eff)
     return [xyzs, dirs, deltas, ts, n_eff]
 
 
@@ -168,8 +163,7 @@ def count_samples(total_samples, counter=None, acc=None):
     float64 (2,) tensor) also acc += (counter[0], the sum): throughput counters kept on the device."""
     check_input(total_samples, "total_samples")
     out = torch.empty((), dtype=torch.int64, device=total_samples.device)
-    call("ncn_count_samples", ptr(total_samples), I64(total_samples.shape[0]), ptr(counter), ptr(out), ptr(acc),
-         stream())
+    call("ncn_count_samples", total_samples, total_samples.shape[0], counter, out, acc)
     return out
 
 
@@ -186,13 +180,12 @@ def composite_train_multi_fw(sigmas, raws, deltas, ts, rays_a, T_threshold, bg=N
     rend = torch.empty(R, C, dtype=torch.float32, device=dev)
     ws = torch.empty(S, dtype=torch.float32, device=dev)
     if bg is None:
-        call("ncn_composite_train_fw", ptr(sigmas), ptr(raws), ptr(deltas), ptr(ts), ptr(rays_a), I64(R), I64(S),
-             I32(C), F32(float(T_threshold)), ptr(total), ptr(opacity), ptr(depth), ptr(rend), ptr(ws), stream())
+        call("ncn_composite_train_fw", sigmas, raws, deltas, ts, rays_a, R, S,
+             C, float(T_threshold), total, opacity, depth, rend, ws)
         return [total, opacity, depth, rend, ws]
     rgb_bg = torch.empty(R, C, dtype=torch.float32, device=dev)
-    call("ncn_composite_train_fw_bg", ptr(sigmas), ptr(raws), ptr(deltas), ptr(ts), ptr(rays_a), I64(R), I64(S),
-         I32(C), F32(float(T_threshold)), ptr(total), ptr(opacity), ptr(depth), ptr(rend), ptr(ws), F32(float(bg)),
-         ptr(rgb_bg), stream())
+    call("ncn_composite_train_fw_bg", sigmas, raws, deltas, ts, rays_a, R, S, C, float(T_threshold), total, opacity,
+         depth, rend, ws, float(bg), rgb_bg)
     return [total, opacity, depth, rend, ws, rgb_bg]
 
 
@@ -212,13 +205,11 @@ def composite_train_multi_bw(dL_dopacity, dL_ddepth, dL_drend, dL_dws, sigmas, r
     dsig = torch.empty(S, dtype=torch.float32, device=sigmas.device)
     draws = torch.empty(S, C, dtype=torch.float32, device=sigmas.device)
     if bg is None:
-        call("ncn_composite_train_bw", ptr(dL_dopacity), ptr(dL_ddepth), ptr(dL_drend), ptr(dL_dws), ptr(sigmas),
-             ptr(raws), ptr(ws), ptr(deltas), ptr(ts), ptr(rays_a), I64(R), I64(S), I32(C), ptr(opacity), ptr(depth),
-             ptr(rend), F32(float(T_threshold)), ptr(dsig), ptr(draws), stream())
+        call("ncn_composite_train_bw", dL_dopacity, dL_ddepth, dL_drend, dL_dws, sigmas, raws, ws, deltas, ts, rays_a,
+             R, S, C, opacity, depth, rend, float(T_threshold), dsig, draws)
     else:
-        call("ncn_composite_train_bw_bg", ptr(dL_dopacity), ptr(dL_ddepth), ptr(dL_drend), ptr(dL_dws), ptr(sigmas),
-             ptr(raws), ptr(ws), ptr(deltas), ptr(ts), ptr(rays_a), I64(R), I64(S), I32(C), ptr(opacity), ptr(depth),
-             ptr(rend), F32(float(T_threshold)), F32(float(bg)), ptr(dsig), ptr(draws), stream())
+        call("ncn_composite_train_bw_bg", dL_dopacity, dL_ddepth, dL_drend, dL_dws, sigmas, raws, ws, deltas, ts,
+             rays_a, R, S, C, opacity, depth, rend, float(T_threshold), float(bg), dsig, draws)
     return [dsig, draws]
 
 
@@ -230,8 +221,8 @@ def composite_test_multi_fw(sigmas, raws, deltas, ts, hits_t, alive_indices, T_t
                  (depth, "depth"), (rend, "rend")):
         check_input(t, n)
     A, N, C = sigmas.shape[0], sigmas.shape[1], raws.shape[2]
-    call("ncn_composite_test_fw", ptr(sigmas), ptr(raws), ptr(deltas), ptr(ts), ptr(alive_indices), I64(A), I32(N),
-         I32(C), F32(float(T_threshold)), ptr(N_eff_samples), ptr(opacity), ptr(depth), ptr(rend), stream())
+    call("ncn_composite_test_fw", sigmas, raws, deltas, ts, alive_indices, A, N,
+         C, float(T_threshold), N_eff_samples, opacity, depth, rend)
 
 
 def distortion_loss_fw(ws, deltas, ts, rays_a):
@@ -242,8 +233,7 @@ def distortion_loss_fw(ws, deltas, ts, rays_a):
     loss = torch.zeros(R, dtype=torch.float32, device=ws.device)
     wsi = torch.zeros(S, dtype=torch.float32, device=ws.device)
     wtsi = torch.zeros(S, dtype=torch.float32, device=ws.device)
-    call("ncn_distortion_loss_fw", ptr(ws), ptr(deltas), ptr(ts), ptr(rays_a), I64(R), ptr(loss), ptr(wsi), ptr(wtsi),
-         stream())
+    call("ncn_distortion_loss_fw", ws, deltas, ts, rays_a, R, loss, wsi, wtsi)
     return [loss, wsi, wtsi]
 
 
@@ -254,6 +244,6 @@ def distortion_loss_bw(dL_dloss, ws_inclusive_scan, wts_inclusive_scan, ws, delt
                  (rays_a, "rays_a")):
         check_input(t, n)
     dws = torch.zeros(ws.shape[0], dtype=torch.float32, device=ws.device)
-    call("ncn_distortion_loss_bw", ptr(dL_dloss), ptr(ws_inclusive_scan), ptr(wts_inclusive_scan), ptr(ws),
-         ptr(deltas), ptr(ts), ptr(rays_a), I64(rays_a.shape[0]), ptr(dws), stream())
+    call("ncn_distortion_loss_bw", dL_dloss, ws_inclusive_scan, wts_inclusive_scan, ws,
+         deltas, ts, rays_a, rays_a.shape[0], dws)
     return dws

@@ -1,17 +1,38 @@
 """The C ABI library: loads on CPU-only hosts and exports every symbol include/ncnerf.h declares
-(no compute calls without a GPU)."""
+(no compute calls without a GPU); the ctypes binding is derived from that header (known answers,
+the parser's strictness) and `call` refuses a wrong argument before anything is launched."""
 import ctypes
 import os
 import re
+
+import numpy as np
+import pytest
+import torch
+
+from ncnerf_amd import _lib
+from ncnerf_amd._lib import F32, F64, I32, I64, P, U32, U64
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "ncnerf.h")
 
 
 def declared_symbols():
+    return sorted(_lib.parse_header(open(HEADER).read()))
+
+
+def scanned_symbols():
+    """Independent of the parser: every `ncn_name(` of the header without comments and directives."""
     text = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(ncn_[a-z0-9_]+)\s*\(", text)))
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)  # (#define NCN_FIELD_NW (... is no declaration)
+    return sorted(set(m.group(1) for m in re.finditer(r"\b(ncn_\w+)\s*\(", text, flags=re.I)))
+
+
+def test_parser_and_scan_agree_on_the_symbols():
+    syms = declared_symbols()
+    assert syms == scanned_symbols()
+    assert len(syms) == 80
+    assert {"ncn_morton3D", "ncn_morton3D_invert", "ncn_field_bwd_dE_floats"} <= set(syms)
 
 
 def test_header_declares_the_hot_path():
@@ -23,14 +44,12 @@ def test_header_declares_the_hot_path():
 
 
 def test_library_exports_every_declared_symbol():
-    from ncnerf_amd import _lib
     L = ctypes.CDLL(_lib.LIB_PATH)
     missing = [s for s in declared_symbols() if not hasattr(L, s)]
     assert not missing, missing
 
 
 def test_python_binding_covers_header():
-    from ncnerf_amd import _lib
     bound = set(_lib.exported_symbols())
     assert set(declared_symbols()) <= bound, set(declared_symbols()) - bound
     L = _lib.lib()
@@ -39,6 +58,197 @@ def test_python_binding_covers_header():
 
 
 def test_library_is_gfx950_code_object():
-    from ncnerf_amd import _lib
     data = open(_lib.LIB_PATH, "rb").read()
     assert b"gfx950" in data
+
+
+# ---- the derived binding: known answers, written out by hand ----
+KNOWN = {
+    # the list INTEGRATION.md §2 prints
+    "ncn_composite_train_fw": [P, P, P, P, P, I64, I64, I32, F32, P, P, P, P, P, P],
+    "ncn_batch_draw": [U64, P, I64, I32, I32, I32, I32, I64, I32, I32, P, P, P],
+    "ncn_grid_packbits": [P, I64, F64, P, P, P, P],
+    "ncn_adam_step_packed": [P, P, P, P, I64, I64, F32, F32, F32, F64, F64, F32, F32, F32, P, P, P, I32, P, P,
+                             P, I64, P, I32, P],
+    "ncn_kmeans_plan_fill": [I32, I32, U32, P],
+    "ncn_step_inputs": [I32, P, P, P, P, I64, P, I32, P],
+}
+NON_INT = {"ncn_last_error": ctypes.c_char_p, "ncn_grid_work_bytes": I64, "ncn_march_train_fused_work_bytes": I64,
+           "ncn_field_bwd_dE_floats": I64, "ncn_field_bwd_stash_floats": I64, "ncn_kmeans_plan_words": I64,
+           "ncn_cluster_workspace_words": I64, "ncn_cluster_status_offset": I64, "ncn_adam_step_work_floats": I64}
+
+
+@pytest.mark.parametrize("name", sorted(KNOWN))
+def test_known_argtypes(name):
+    fn = getattr(_lib.lib(), name)
+    assert _lib.SIGNATURES[name] == KNOWN[name]
+    assert list(fn.argtypes) == KNOWN[name] and fn.restype is ctypes.c_int
+    assert len(KNOWN["ncn_adam_step_packed"]) == 25 and KNOWN["ncn_adam_step_packed"].count(F64) == 2
+
+
+def test_known_restypes():
+    L = _lib.lib()
+    got = {n: getattr(L, n).restype for n in _lib.exported_symbols() if getattr(L, n).restype is not ctypes.c_int}
+    assert got == NON_INT
+
+
+def test_parse_result_shape():
+    abi = _lib.parse_header(open(HEADER).read())
+    assert abi["ncn_morton3D"] == ("int", [("ptr", 4, "coords"), ("int64_t", 0, "n"), ("ptr", 4, "out"),
+                                           ("ptr", 0, "stream")])
+    assert abi["ncn_last_error"] == ("const char*", []) and abi["ncn_grid_work_bytes"] == ("int64_t", [])
+    assert abi["ncn_step_inputs"][1][1:3] == [("ptr", 8, "src"), ("ptr", 8, "dst")]
+    assert abi["ncn_field_fwd"][1][9] == ("ptr", 2, "weights_packed")
+
+
+@pytest.mark.parametrize("header", [
+    "int ncn_x(size_t n);",
+    "int ncn_x(const float*);",
+    "int ncn_x(int (*cb)(int));",
+    "struct S ncn_x(int a);",
+    "int ncn_x(int a)\nint ncn_y(int b);",
+    "int ncn_x(int a)",
+    "int ncn_x(inta);",
+    "int ncn_x(float** a);",
+    "unsigned ncn_x(int a);",
+    "int ncn_x(int a); int ncn_x(int a);",
+])
+def test_parser_is_strict(header):
+    with pytest.raises(ValueError, match="ncn_x"):
+        _lib.parse_header(header)
+
+
+def test_parser_accepts_the_grammar():
+    abi = _lib.parse_header('/* c */\n#include <stdint.h>\nextern "C" {\nint64_t ncn_a(void);\n'
+                            "const char* ncn_b(const void* const* p, double d /* why */, uint8_t *q); // x\n}\n")
+    assert abi == {"ncn_a": ("int64_t", []),
+                   "ncn_b": ("const char*", [("ptr", 8, "p"), ("double", 0, "d"), ("ptr", 1, "q")])}
+
+
+# ---- marshalling: every refusal precedes the call, so none of this needs a GPU ----
+@pytest.fixture
+def streams(monkeypatch):
+    """_lib.stream replaced by a counter: how often the current stream was fetched."""
+    fetched = []
+
+    def fake_stream():
+        fetched.append(1)
+        return P(0x5EED)
+    monkeypatch.setattr(_lib, "stream", fake_stream)
+    return fetched
+
+
+def test_wrong_argument_count(streams):
+    dev_like = P(16)
+    for args in ((dev_like, 8), (dev_like, 8, dev_like, P(0), 1), ()):  # too few by two, too many, none
+        with pytest.raises(TypeError, match=r"ncn_morton3D.*coords.*stream"):
+            _lib.marshal("ncn_morton3D", args)
+    with pytest.raises(TypeError, match="ncn_kmeans_plan_fill"):  # a host function has no stream to leave out
+        _lib.marshal("ncn_kmeans_plan_fill", (1, 2, 3))
+    assert not streams
+
+
+def test_scalars(streams):
+    buf = torch.zeros(8, dtype=torch.int32)
+    with pytest.raises(TypeError, match=r"ncn_kmeans_plan_fill: argument 0 \(n_tri\).*int.*float 3.0"):
+        _lib.marshal("ncn_kmeans_plan_fill", (3.0, 2, 1234, buf))  # a float for an integer
+    for tensor in (torch.tensor(3), torch.tensor([3]), torch.tensor(3.0)):  # a tensor for a scalar, int or float
+        with pytest.raises(TypeError, match=r"argument 0 \(n_tri\)"):
+            _lib.marshal("ncn_kmeans_plan_fill", (tensor, 2, 1234, buf))
+        with pytest.raises(TypeError, match=r"ncn_packbits: argument 2 \(threshold\)"):
+            _lib.marshal("ncn_packbits", (P(16), 8, tensor, P(16), P(0)))
+    with pytest.raises(TypeError, match=r"argument 2 \(threshold\)"):
+        _lib.marshal("ncn_packbits", (P(16), 8, "0.5", P(16), P(0)))
+    out = _lib.marshal("ncn_packbits", (P(16), np.int64(8), 1, P(16), P(0)))  # index() and float() conversions
+    assert type(out[1]) is int and out[1] == 8 and type(out[2]) is float and out[2] == 1.0
+    assert _lib.marshal("ncn_kmeans_plan_fill", (True, 2, 1234, buf))[0] == 1
+    assert not streams
+
+
+def test_pointers(streams):
+    i32, i64 = torch.zeros(8, dtype=torch.int32), torch.zeros(8, dtype=torch.int64)
+    # a host function takes CPU tensors of the pointee's width
+    assert _lib.marshal("ncn_kmeans_plan_fill", (1, 2, 3, i32)) == (1, 2, 3, i32.data_ptr())
+    with pytest.raises(TypeError, match=r"ncn_kmeans_plan_fill: argument 3 \(host_out\).*4-byte.*int64 cpu tensor"):
+        _lib.marshal("ncn_kmeans_plan_fill", (1, 2, 3, i64))
+    # a launching function takes CUDA tensors only, whichever pointer it is
+    for args in ((i32, 8, P(16)), (P(16), 8, i32)):
+        with pytest.raises(TypeError, match=r"ncn_morton3D: argument [02] \((coords|out)\).*CUDA.*cpu tensor"):
+            _lib.marshal("ncn_morton3D", args)
+    # the width is all that is checked: fp16 and bf16 both pass for uint16_t*, float32 for a uint32_t*
+    # workspace, anything for void* (a host function of its own, so that CPU tensors are accepted)
+    params = _lib.parse_header("int ncn_t(const uint16_t* h, uint32_t* w, const void* v, double* d);")["ncn_t"][1]
+    fn, counts = _lib._marshaller("ncn_t", params)
+    w, f64 = torch.zeros(2), torch.zeros(2, dtype=torch.float64)
+    for h in (torch.zeros(2, dtype=torch.float16), torch.zeros(2, dtype=torch.bfloat16)):
+        for v in (h, i32, f64, torch.zeros(2, dtype=torch.uint8)):
+            assert fn(h, w, v, f64) == (h.data_ptr(), w.data_ptr(), v.data_ptr(), f64.data_ptr())
+    assert counts == (4,)
+    with pytest.raises(TypeError, match=r"argument 0 \(wire\).*2-byte"):
+        _lib.marshal("ncn_grad_unpack_f16", (torch.zeros(2), 2, None, None))
+    # a bare int and a numpy array are no pointers
+    for bad in (i32.data_ptr(), np.zeros(8, np.int32), [1, 2], "x"):
+        with pytest.raises(TypeError, match=r"argument 3 \(host_out\)"):
+            _lib.marshal("ncn_kmeans_plan_fill", (1, 2, 3, bad))
+    assert _lib.marshal("ncn_kmeans_plan_fill", (1, 2, 3, None))[3] is None  # NULL
+    assert not streams
+
+
+def test_ctypes_instances_pass_untouched(streams):
+    arr = (ctypes.c_void_p * 2)()
+    cap = ctypes.c_int(0)
+    args = (I32(2), arr, ctypes.cast(arr, P), ctypes.byref(cap), P(None), I64(5), P(16), I32(1), P(0x77))
+    out = _lib.marshal("ncn_step_inputs", args)
+    assert len(out) == 9 and all(a is b for a, b in zip(out, args))
+    args = (U64(1), P(None), I64(0), I32(1), I32(8), I32(8), I32(2), I64(4), I32(0), I32(0), P(16), P(16), P(0x77))
+    assert all(a is b for a, b in zip(_lib.marshal("ncn_batch_draw", args), args))
+    args = (P(16), I64(8), F64(0.5), P(16), P(16), P(16), P(0x77))
+    assert all(a is b for a, b in zip(_lib.marshal("ncn_grid_packbits", args), args))
+    assert _lib.marshal("ncn_packbits", (P(16), 8, F32(0.5), P(16), P(0)))[2].value == 0.5
+    assert _lib.marshal("ncn_kmeans_plan_fill", (1, 2, U32(3), P(16)))[2].value == 3
+    assert not streams  # full-length lists: used as given
+
+
+def test_stream_appended_only_when_exactly_one_is_missing(streams):
+    out = _lib.marshal("ncn_morton3D", (P(16), 8, P(32)))
+    assert len(out) == 4 and out[3].value == 0x5EED and len(streams) == 1
+    mine = P(0x77)
+    assert _lib.marshal("ncn_morton3D", (P(16), 8, P(32), mine))[3] is mine and len(streams) == 1
+    with pytest.raises(TypeError):
+        _lib.marshal("ncn_morton3D", (P(16), 8.5, P(32)))  # refused before the stream is fetched
+    assert len(streams) == 1
+
+
+def test_a_refused_call_never_reaches_the_library(streams, monkeypatch):
+    monkeypatch.setattr(_lib, "lib", lambda: pytest.fail("the library was entered"))
+    with pytest.raises(TypeError):
+        _lib.call("ncn_morton3D", torch.zeros(8, 3, dtype=torch.int32), 8, torch.zeros(8, dtype=torch.int32))
+    with pytest.raises(TypeError):
+        _lib.call("ncn_kmeans_plan_fill", 1, 2, 3)
+    assert not streams
+
+
+def test_missing_header_names_the_path(monkeypatch, tmp_path):
+    monkeypatch.setattr(_lib, "HEADER_PATH", str(tmp_path / "include" / "ncnerf.h"))
+    with pytest.raises(_lib.NcnError, match=re.escape(str(tmp_path / "include" / "ncnerf.h"))):
+        _lib._read_header()
+
+
+@pytest.mark.gpu
+def test_morton3D_through_call():
+    """ncn_morton3D, 8 coordinates: the stream omitted == stream() passed; an int64 `coords` is a
+    TypeError and launches nothing (the sentinel-filled output is untouched after a synchronise)."""
+    dev = torch.device("cuda:0")
+    coords = torch.tensor([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1], [1, 1, 1], [5, 9, 127], [127, 127, 127],
+                           [64, 3, 77]], dtype=torch.int32, device=dev)
+    a = torch.full((8,), -7, dtype=torch.int32, device=dev)
+    b = torch.full((8,), -7, dtype=torch.int32, device=dev)
+    _lib.call("ncn_morton3D", coords, 8, a)
+    _lib.call("ncn_morton3D", coords, 8, b, _lib.stream())
+    torch.cuda.synchronize()
+    assert torch.equal(a, b) and a[0] == 0 and a[4] == 7 and a[6] == 2 ** 21 - 1 and -7 not in a.tolist()
+    out = torch.full((8,), -7, dtype=torch.int32, device=dev)
+    with pytest.raises(TypeError, match=r"ncn_morton3D: argument 0 \(coords\)"):
+        _lib.call("ncn_morton3D", coords.long(), 8, out)
+    torch.cuda.synchronize()
+    assert out.tolist() == [-7] * 8

@@ -209,8 +209,7 @@ def test_image_normals_small_shapes(dev, H, W):
     rot = make_cameras(2, seed=1)[:, :, :3]
     out = torch.full((2, H, W, 3), 7.0, device=dev)  # every element is written
     dd, qd, rd = _dev(depth, dev), _dev(dirs, dev), _dev(rot, dev)
-    _lib.call("ncn_depth_normals_image", _lib.ptr(dd), _lib.ptr(qd), _lib.ptr(rd), _lib.I32(2), _lib.I32(H), _lib.I32(W),
-              _lib.ptr(out), _lib.stream())
+    _lib.call("ncn_depth_normals_image", dd, qd, rd, 2, H, W, out)
     got = out.cpu().numpy()
     border = np.ones((H, W), bool)
     border[1:-1, 1:-1] = False
@@ -258,8 +257,7 @@ def test_assign_at_scale(dev):
     Xd, Cd = _dev(X, dev), _dev(C, dev)
     assign = torch.full((n + 64,), -5, dtype=torch.int32, device=dev)
     counts = torch.full((K + 2,), -5, dtype=torch.int64, device=dev)
-    _lib.call("ncn_kmeans_assign", _lib.ptr(Xd), _lib.I64(n), _lib.ptr(Cd), _lib.I32(K), _lib.ptr(assign),
-              _lib.ptr(counts), _lib.stream())
+    _lib.call("ncn_kmeans_assign", Xd, n, Cd, K, assign, counts)
     got, cnt = assign.cpu().numpy(), counts.cpu().numpy()
     assert np.array_equal(got[:n], ref)
     assert np.all(got[n:] == -5) and np.all(cnt[K:] == -5)  # nothing written past the ends

@@ -225,14 +225,12 @@ def test_field_morton_window_order(dev, n):
     form a run depends on the processing order: 32-bit sums at 2^-(30 - log2(unit) - e) of the
     level's max |dE|, so relative L2 <= 2e-4 for the table block, 1e-5 for the MLP weights)."""
     from ncnerf_amd import _lib
-    from ncnerf_amd._lib import F32, I64, ptr, stream
     P, _ = field_ref.init_params(seed=5, table_init=0.5)
     m = _model_from_oracle(P, dev)
     x, d = _inputs(n, 3)
     x, d = x.to(dev), d.to(dev)
     order = torch.empty(n, dtype=torch.int32, device=dev)
-    assert _lib.lib().ncn_field_sort_windows(ptr(x), I64(n), ptr(None), F32(m._xyz_min), F32(m._xyz_extent),
-                                             ptr(order), stream()) == 0
+    assert _lib.call("ncn_field_sort_windows", x, n, None, m._xyz_min, m._xyz_extent, order) == 0
     check_window_order(order.cpu().numpy().astype(np.int64), x.cpu().numpy(), m._xyz_min, m._xyz_extent)
 
     def run(sort):
@@ -258,7 +256,6 @@ def test_density_level_split_mode_bitexact(dev, precision):
     XCDs into a scratch, then sigma_net) == mode 1 (sample-major) bit for bit, with a device count
     below the capacity (points past it untouched) and a count that is not a multiple of 16."""
     from ncnerf_amd import _lib
-    from ncnerf_amd._lib import F32, I32, I64, ptr, stream
     from ncnerf_amd import vren
     m = NGPMT(scale=0.5, grid_size=128, precision=precision).to(dev)
     with torch.no_grad():
@@ -275,9 +272,8 @@ def test_density_level_split_mode_bitexact(dev, precision):
         for mode in (1, 2):
             sig = torch.full((cap,), -7.0, device=dev)
             enc = torch.empty(cap * 32, dtype=torch.float16, device=dev) if mode == 2 else None
-            _lib.call("ncn_field_fwd", ptr(pts), ptr(None), I64(cap), ptr(n_dev), ptr(None), ptr(table),
-                      m._levels_ptr, F32(m._xyz_min), F32(m._xyz_extent), ptr(packed), I32(m._prec), I32(mode),
-                      ptr(sig), ptr(None), ptr(enc), stream())
+            _lib.call("ncn_field_fwd", pts, None, cap, n_dev, None, table, m._levels_ptr, m._xyz_min, m._xyz_extent,
+                      packed, m._prec, mode, sig, None, enc)
             out.append(sig)
         torch.cuda.synchronize()
         assert torch.equal(out[0], out[1]), (precision, count)

@@ -49,7 +49,6 @@ import torch
 from oracle import field_ref
 from field_level_check import outlier_mask, outlier_share, place_edges
 from ncnerf_amd import _lib
-from ncnerf_amd._lib import F32, I32, I64, ptr, stream
 from ncnerf_amd.ngp_mt import ENC_BYTES, N_W
 from test_gpu_field import TOL, _inputs, _model_from_oracle, check_window_order
 from test_gpu_scatter_units import _check, _ray_samples, scatter_case
@@ -96,8 +95,7 @@ def _model(dev, precision):
 def _sort_windows(m, x):
     n = x.shape[0]
     order = torch.empty(n, dtype=torch.int32, device=x.device)
-    assert _lib.lib().ncn_field_sort_windows(ptr(x), I64(n), ptr(None), F32(m._xyz_min), F32(m._xyz_extent), ptr(order),
-                                             stream()) == 0
+    assert _lib.call("ncn_field_sort_windows", x, n, None, m._xyz_min, m._xyz_extent, order) == 0
     return order
 
 
@@ -112,16 +110,16 @@ def _mlp_pass(m, x, d, dsig, drgb, n_dev=None, order=None, ws=None):
     sig = torch.zeros(n, device=dev)
     rgb = torch.zeros(n, 3, device=dev)
     enc = torch.zeros(((n + 15) // 16) * 16 * ENC_BYTES // 2, dtype=torch.float16, device=dev)
-    _lib.call("ncn_field_fwd", ptr(x), ptr(d), I64(n), ptr(n_dev), ptr(order), ptr(table), m._levels_ptr,
-              F32(m._xyz_min), F32(m._xyz_extent), ptr(packed), I32(m._prec), I32(0), ptr(sig), ptr(rgb), ptr(enc), stream())
-    nb = int(L.ncn_field_bwd_blocks(I64(n)))
+    _lib.call("ncn_field_fwd", x, d, n, n_dev, order, table, m._levels_ptr,
+              m._xyz_min, m._xyz_extent, packed, m._prec, 0, sig, rgb, enc)
+    nb = int(L.ncn_field_bwd_blocks(n))
     slab = torch.empty(nb * N_W, device=dev)
     if ws is None:
-        ws = torch.zeros(int(L.ncn_field_bwd_dE_floats(I64(n))), device=dev)
+        ws = torch.zeros(int(L.ncn_field_bwd_dE_floats(n)), device=dev)
         ws[-32:] = 7.0  # (the unit queue: the MLP pass must zero it)
     lmax = torch.full((256, 16), -1.0, device=dev)
-    _lib.call("ncn_field_bwd_mlp", ptr(x), ptr(d), I64(n), ptr(n_dev), ptr(order), ptr(packed), I32(m._prec), ptr(enc),
-              ptr(dsig), ptr(drgb), ptr(m._bwd_loss_scale()), ptr(slab), ptr(ws), ptr(lmax), stream())
+    _lib.call("ncn_field_bwd_mlp", x, d, n, n_dev, order, packed, m._prec, enc,
+              dsig, drgb, m._bwd_loss_scale(), slab, ws, lmax)
     torch.cuda.synchronize()
     return ws, lmax, sig, rgb
 
@@ -149,7 +147,7 @@ def _check_header(ws, precision, mask):
 def _check_level_max(lmax, dE, n, n_valid=None):
     """amax over the launched workgroups' rows == max |decoded dE| per level, bit for bit; rows past
     the launched grid untouched."""
-    nb = int(_lib.lib().ncn_field_bwd_blocks(I64(n)))
+    nb = int(_lib.lib().ncn_field_bwd_blocks(n))
     lm = lmax.cpu()
     assert bool((lm[:nb] >= 0).all()) and bool((lm[nb:] == -1.0).all())
     want = dE[:n_valid].reshape(-1, 16, 2).abs().amax(dim=(0, 2))
@@ -266,8 +264,8 @@ def test_scatter_on_the_mlp_pass_workspace(dev, precision, positions):
     _, dE, _ = _decode(ws, n, precision)
     _check_level_max(lmax, dE, n)
     grad = torch.zeros(m._n_table // 2, 2, device=dev)
-    rc = _lib.lib().ncn_field_scatter(ptr(xd), I64(n), ptr(None), ptr(None), m._levels_ptr, F32(m._xyz_min),
-                                      F32(m._xyz_extent), ptr(ws), ptr(lmax), I32(0), I32(16), I32(0), ptr(grad), stream())
+    rc = _lib.call("ncn_field_scatter", xd, n, None, None, m._levels_ptr, m._xyz_min,
+                   m._xyz_extent, ws, lmax, 0, 16, 0, grad)
     assert rc == 0, _lib.lib().ncn_last_error()
     torch.cuda.synchronize()
     assert float(ws[2]) == 3.0
@@ -335,9 +333,8 @@ def test_forward_on_the_edge_set(dev, precision):
         for mode in (1, 2):
             s = torch.full((n,), -7.0, device=dev)
             enc = torch.empty(((n + 15) // 16) * 16 * 32, dtype=torch.float16, device=dev) if mode == 2 else None
-            _lib.call("ncn_field_fwd", ptr(xd), ptr(None), I64(n), ptr(n_dev), ptr(None), ptr(table), m._levels_ptr,
-                      F32(m._xyz_min), F32(m._xyz_extent), ptr(packed), I32(m._prec), I32(mode), ptr(s), ptr(None), ptr(enc),
-                      stream())
+            _lib.call("ncn_field_fwd", xd, None, n, n_dev, None, table, m._levels_ptr,
+                      m._xyz_min, m._xyz_extent, packed, m._prec, mode, s, None, enc)
             res.append(s)
         torch.cuda.synchronize()
         assert torch.equal(res[0], res[1]), (precision, count)

@@ -145,7 +145,6 @@ def test_adam_step_packed_matches_pack_weights(dev, precision):
     from them even if the buffer was stale) and a gated-off deferred step; and the parameters equal
     those of ncn_adam_step without the fold."""
     from ncnerf_amd import _lib
-    from ncnerf_amd._lib import I32, ptr, stream
     from ncnerf_amd.ngp_mt import NGPMT, N_PACKED_HALVES
     torch.manual_seed(0)
     m = NGPMT(scale=0.5, grid_size=128, precision=precision).to(dev)
@@ -162,7 +161,7 @@ def test_adam_step_packed_matches_pack_weights(dev, precision):
 
     def expected():
         out = torch.empty(N_PACKED_HALVES, dtype=torch.float16, device=dev)
-        assert _lib.lib().ncn_field_pack_weights(ptr(flat[m._n_table:]), ptr(out), I32(m._prec), stream()) == 0
+        assert _lib.call("ncn_field_pack_weights", flat[m._n_table:], out, m._prec) == 0
         return out
 
     g = torch.Generator(device=dev).manual_seed(3)

@@ -17,7 +17,6 @@ import torch
 
 from oracle import field_ref
 from ncnerf_amd import _lib
-from ncnerf_amd._lib import F32, I32, I64, ptr, stream
 from ncnerf_amd.ngp_mt import NGPMT
 
 pytestmark = pytest.mark.gpu
@@ -62,8 +61,7 @@ def scatter_case(dev, n, op, mode, xw=None, with_order=False, inf_level=12):
     order = None
     if with_order:
         order = torch.empty(n, dtype=torch.int32, device=dev)
-        assert _lib.lib().ncn_field_sort_windows(ptr(xyzs), I64(n), ptr(None), F32(m._xyz_min), F32(m._xyz_extent),
-                                                 ptr(order), stream()) == 0
+        assert _lib.call("ncn_field_sort_windows", xyzs, n, None, m._xyz_min, m._xyz_extent, order) == 0
     x01 = (xw + np.float32(0.5)).astype(np.float32)  # what the kernel forms: (x - xyz_min) * (1 / extent), extent 1
     rng = np.random.default_rng(n + 1)
     tdt = torch.float16 if op == "fp16" else torch.bfloat16
@@ -78,14 +76,14 @@ def scatter_case(dev, n, op, mode, xw=None, with_order=False, inf_level=12):
     # the dE workspace: header {1 / S, operand type (0 fp16, 1 bf16)}, then level-major [16][n_stride]
     # pairs of the operand type
     n_stride = (n + 3) & ~3
-    ws = torch.zeros(int(_lib.lib().ncn_field_bwd_dE_floats(I64(n))), dtype=torch.float32)
+    ws = torch.zeros(int(_lib.lib().ncn_field_bwd_dE_floats(n)), dtype=torch.float32)
     ws[0] = 1.0 / S
     ws[1] = 0.0 if op == "fp16" else 1.0
     pairs = torch.zeros(16, n_stride, 2, dtype=tdt)
     pairs[:, :n] = gt_.permute(1, 0, 2)
     ws[4:4 + 16 * n_stride] = pairs.contiguous().view(torch.float32).reshape(-1)  # (the scatter fills the rest)
     ws = ws.to(dev)
-    lm_rows = int(_lib.lib().ncn_field_bwd_blocks(I64(n)))
+    lm_rows = int(_lib.lib().ncn_field_bwd_blocks(n))
     lmax = torch.zeros(lm_rows, 16, dtype=torch.float32)
     lmax[0] = torch.from_numpy(np.abs(g).max(axis=(0, 2)))  # (inf on the overflowed level, as the MLP pass records)
     lmax = lmax.to(dev)
@@ -105,11 +103,10 @@ def scatter_case(dev, n, op, mode, xw=None, with_order=False, inf_level=12):
     # (with an order the scatter gathers the positions through it and reads no permuted copy)
     for permuted in ((False,) if with_order else (False, True)):
         if permuted:
-            assert _lib.lib().ncn_field_scatter_positions(ptr(xyzs), I64(n), ptr(None), ptr(ws), stream()) == 0
+            assert _lib.call("ncn_field_scatter_positions", xyzs, n, None, ws) == 0
         grad = torch.zeros(m._n_table, 2, dtype=torch.float32, device=dev)
-        rc = _lib.lib().ncn_field_scatter(ptr(xyzs), I64(n), ptr(None), ptr(order), m._levels_ptr, F32(m._xyz_min),
-                                          F32(m._xyz_extent), ptr(ws), ptr(lmax), I32(0), I32(16), I32(0), ptr(grad),
-                                          stream())
+        rc = _lib.call("ncn_field_scatter", xyzs, n, None, order, m._levels_ptr, m._xyz_min,
+                       m._xyz_extent, ws, lmax, 0, 16, 0, grad)
         assert rc == 0, _lib.lib().ncn_last_error()
         torch.cuda.synchronize()
         assert float(ws[2]) == (15.0 if permuted else 0.0)  # (the mask of the four unit classes)

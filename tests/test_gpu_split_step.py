@@ -16,7 +16,6 @@ import pytest
 import torch
 
 from ncnerf_amd import _lib
-from ncnerf_amd._lib import I32, I64, ptr, stream
 from ncnerf_amd.ngp_mt import N_W, NGPMT, register_grid_buffers
 from ncnerf_amd.rendering import render
 from ncnerf_amd.split_step import SplitStep, split_eligible
@@ -55,36 +54,34 @@ def test_mlp_parts_equal_one_pass(dev, precision, n, sort):
     dsig = torch.randn(n, device=dev, generator=g) * 1e-2
     drgb = torch.randn(n, 3, device=dev, generator=g) * 1e-2
     L = _lib.lib()
-    nb_full = int(L.ncn_field_bwd_blocks(I64(n)))
-    dE_n = int(L.ncn_field_bwd_dE_floats(I64(n)))
+    nb_full = int(L.ncn_field_bwd_blocks(n))
+    dE_n = int(L.ncn_field_bwd_dE_floats(n))
     scale = m._bwd_loss_scale()
 
     def one_pass():
         slab = torch.full((nb_full * N_W,), float("nan"), device=dev)
         dE = torch.zeros(dE_n, device=dev)
         lmax = torch.full((16 * 256,), -1.0, device=dev)
-        _lib.call("ncn_field_bwd_mlp", ptr(x), ptr(d), I64(n), ptr(n_dev), ptr(order), ptr(packed), I32(m._prec), ptr(enc),
-                  ptr(dsig), ptr(drgb), ptr(scale), ptr(slab), ptr(dE), ptr(lmax), stream())
+        _lib.call("ncn_field_bwd_mlp", x, d, n, n_dev, order, packed, m._prec, enc, dsig, drgb, scale, slab, dE, lmax)
         return slab, dE, lmax
 
     def parts(nb1, nb2):
-        g1 = nb1 or int(L.ncn_field_bwd_part_blocks(I64(n), I32(1)))
-        g2 = nb2 or int(L.ncn_field_bwd_part_blocks(I64(n), I32(2)))
+        g1 = nb1 or int(L.ncn_field_bwd_part_blocks(n, 1))
+        g2 = nb2 or int(L.ncn_field_bwd_part_blocks(n, 2))
         slab = torch.full((max(g1, g2) * N_W,), float("nan"), device=dev)
         dE = torch.zeros(dE_n, device=dev)
         lmax = torch.full((16 * 256,), -1.0, device=dev)
-        stash = torch.empty(int(L.ncn_field_bwd_stash_floats(I64(n))), device=dev)
+        stash = torch.empty(int(L.ncn_field_bwd_stash_floats(n)), device=dev)
         for part, ds, nb in ((1, None, nb1), (2, dsig, nb2)):
-            _lib.call("ncn_field_bwd_mlp_part", ptr(x), ptr(d), I64(n), ptr(n_dev), ptr(order), ptr(packed), I32(m._prec),
-                      ptr(enc), ptr(ds), ptr(None), ptr(drgb), ptr(scale), I32(part), I32(nb), ptr(slab), ptr(dE),
-                      ptr(lmax), ptr(stash), stream())
+            _lib.call("ncn_field_bwd_mlp_part", x, d, n, n_dev, order, packed, m._prec, enc, ds, None, drgb, scale,
+                      part, nb, slab, dE, lmax, stash)
         w = torch.zeros(N_W, device=dev)
-        _lib.call("ncn_field_reduce_wgrad_parts", ptr(slab), I32(g2), I32(g1), ptr(w), stream())
+        _lib.call("ncn_field_reduce_wgrad_parts", slab, g2, g1, w)
         return slab, dE, lmax, w
 
     s0, e0, l0 = one_pass()
     w0 = torch.zeros(N_W, device=dev)
-    _lib.call("ncn_field_reduce_wgrad", ptr(s0), I32(nb_full), ptr(w0), stream())
+    _lib.call("ncn_field_reduce_wgrad", s0, nb_full, w0)
     s1, e1, l1, _ = parts(nb_full, nb_full)
     torch.cuda.synchronize()
     assert torch.equal(s0, s1)  # every tile written, by one of the two passes, bit for bit

@@ -8,7 +8,6 @@ import torch
 
 from oracle import losses_ref as L
 from ncnerf_amd import _lib
-from ncnerf_amd._lib import I32, U32, ptr
 
 
 def test_mt19937_known_answer():
@@ -21,9 +20,9 @@ def test_mt19937_known_answer():
 
 def _plan(n_tri, K, seed=1234):
     lib = _lib.lib()
-    words = int(lib.ncn_kmeans_plan_words(I32(n_tri), I32(K)))
+    words = int(lib.ncn_kmeans_plan_words(n_tri, K))
     buf = torch.zeros(words, dtype=torch.int32)
-    assert lib.ncn_kmeans_plan_fill(I32(n_tri), I32(K), U32(seed), ptr(buf)) == 0
+    assert _lib.call("ncn_kmeans_plan_fill", n_tri, K, seed, buf) == 0
     return buf.numpy().view(np.uint32)
 
 
