@@ -426,7 +426,10 @@ int ncn_kmeans_plan_fill(int n_tri, int K, uint32_t seed, uint32_t* host_out);
 /* Validity filter, spherical k-means (K in {10,20}, niter Lloyd iterations), cluster selection,
  * the three cluster losses and their gradient w.r.t. the normals, scaled by w_ort / w_dot / w_l1,
  * in ONE launch of 16 co-resident workgroups (KM_BLOCKS in csrc/loss.hip; tagged partial words between
- * the Lloyd rounds, grid barriers between the later phases).  n_tri <= 16384.
+ * the Lloyd rounds, grid barriers between the later phases).  n_tri <= 16384, unit normals.
+ * niter in [0, 30]; 0 = faiss with no iteration: the init picks, renormalised (post_process_centroids
+ * precedes the loop in Clustering::train), and the final search.  With exactly K valid normals
+ * faiss copies them as the centroids, in order and not renormalised, whatever niter is.
  * kmeans_plan: device copy of ncn_kmeans_plan_fill(n_tri, K, seed) (a mismatched plan sets the
  * status word, ncn_cluster_status_offset).
  * out_losses (11 floats): [0..2] = unweighted (ort, centr_dot, centr_L1) after the validity filter;

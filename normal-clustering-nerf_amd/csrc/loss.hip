@@ -458,23 +458,38 @@ __device__ __forceinline__ void sum_partials(const long long* __restrict__ p, in
 }
 
 // Lloyd-round partials are published as TAGGED words instead of behind a grid barrier: each
-// int64 word = tag << 50 | (fixed-point value mod 2^50), value = sum * 2^39 (a workgroup's sum of
-// at most KM_CHUNK_MAX = 512 unit components: |value| <= 2^48; the precision of the barrier-based
-// 2^40 sums within a factor 2).  tag = ((launch sequence + 1) mod 2^9) << 5 | round; every launch
-// writes every word of both buffers (a launch that does not cluster writes void tags), so a word
-// is never older than the previous launch and 9 sequence bits cannot alias,
-// so a reader polls the words themselves until all KM_BLOCKS rows carry the round's tag: one
+// int64 word = tag << 51 | (fixed-point value mod 2^51), value = sum * 2^39, read back as a SIGNED
+// 51-bit field.  A workgroup sums at most KM_CHUNK_MAX = 1024 components of unit normals (|x| <= 1;
+// the count word adds 1.0 per point), so |value| <= 1024 * 2^39 = 2^49, reached with either sign
+// when a whole chunk is one cluster of axis-aligned normals (a wall in a patch-ordered batch); the
+// field holds [-2^50, 2^50) (static_assert below).  (A 50-bit field, [-2^49, 2^49), read +2^49 as
+// -2^49.)  The precision of the barrier-based 2^40 sums within a factor 2.
+// tag (13 bits) = ((launch sequence + 1) mod 2^8) << 5 | round.  What a reader of (sequence s,
+// round it) can find in a word of buffer it & 1: this launch's rounds it - 2, it - 4, ... or its
+// void word (another round field: rounds are 0..30, void is 31); never this launch's round it + 2
+// (double buffering, below); or the previous launch's word (sequence s - 1: another sequence field
+// for any width >= 1 bit).  Nothing older: every launch writes every word of both buffers (a
+// launch that does not cluster, or clusters with no Lloyd round, writes void tags), so a word is
+// never older than the previous launch and the 8 sequence bits cannot alias when they wrap.
+// So a reader polls the words themselves until all KM_BLOCKS rows carry the round's tag: one
 // store and (usually) one load round trip per round instead of store + arrive + poll + load.
 // The rows are double-buffered by round parity: a workgroup writes round it+2 only after it read
 // round it+1 from every workgroup, each of which published it+1 only after reading round it.
 constexpr double KM_FXL = 549755813888.0;  // 2^39
-constexpr int KM_TAG_SHIFT = 50;
+constexpr int KM_TAG_SHIFT = 51;
+constexpr int KM_ROUND_BITS = 5;
+constexpr int KM_SEQ_BITS = 64 - KM_TAG_SHIFT - KM_ROUND_BITS;
 constexpr unsigned long long KM_VMASK = (1ull << KM_TAG_SHIFT) - 1;
 constexpr unsigned KM_VOID_ROUND = 31;  // round field of the void words (niter <= 30)
+static_assert((double)KM_CHUNK_MAX * KM_FXL <= (double)((1ull << (KM_TAG_SHIFT - 1)) - 1),
+              "a workgroup's Lloyd partial (KM_CHUNK_MAX unit components at scale KM_FXL) must fit the signed value field");
+static_assert(KM_SEQ_BITS >= 1 && KM_VOID_ROUND < (1u << KM_ROUND_BITS), "tag = sequence | round");
 __device__ __forceinline__ long long km_tagged(unsigned tag, long long v) {
     return (long long)(((unsigned long long)tag << KM_TAG_SHIFT) | ((unsigned long long)v & KM_VMASK));
 }
-__device__ __forceinline__ unsigned km_round_tag(unsigned seq, int it) { return (((seq + 1u) & 0x1FFu) << 5) | (unsigned)it; }
+__device__ __forceinline__ unsigned km_round_tag(unsigned seq, int it) {
+    return (((seq + 1u) & ((1u << KM_SEQ_BITS) - 1u)) << KM_ROUND_BITS) | (unsigned)it;
+}
 // Exact sum of the KM_BLOCKS tagged words p[b * row + off] once every one carries `tag` (bounded
 // poll: a row that never arrives sets the error word, as km_grid_sync does).
 __device__ __forceinline__ float sum_rows_tagged(const long long* __restrict__ p, int row, int off, unsigned tag,
@@ -495,7 +510,7 @@ __device__ __forceinline__ float sum_rows_tagged(const long long* __restrict__ p
     }
     long long a = 0;
 #pragma unroll
-    for (int b = 0; b < KM_BLOCKS; b++)  // sign-extend the 50-bit values
+    for (int b = 0; b < KM_BLOCKS; b++)  // sign-extend the KM_TAG_SHIFT-bit values
         a += (long long)((unsigned long long)v[b] << (64 - KM_TAG_SHIFT)) >> (64 - KM_TAG_SHIFT);
     return (float)((double)a * (1.0 / KM_FXL));
 }
@@ -895,11 +910,14 @@ __global__ __launch_bounds__(KM_THREADS) void cluster_kernel(
 #pragma unroll
             for (int q = 0; q < 3; q++) L.pv[q][j] = normals[3 * i + q];
         }
-    if (clustered && tid < K) {  // faiss: centroids = the picked points, post-processed (renormalised)
+    if (clustered && tid < K) {
+        // faiss Clustering::train: centroids = the picked points, then post_process_centroids
+        // (renormalised) BEFORE the iteration loop, so also at niter = 0; only the nx == k corner
+        // returns the copied points untouched
         float c[3];
 #pragma unroll
         for (int q = 0; q < 3; q++) c[q] = regs ? L.pickv[tid][q] : normals[3 * L.picki[tid] + q];
-        if (niter_eff > 0) faiss_renorm3(c);
+        if (n_train != K) faiss_renorm3(c);
 #pragma unroll
         for (int q = 0; q < 3; q++) L.C[tid][q] = c[q];
     }

@@ -205,7 +205,7 @@ def spherical_kmeans(X, K=KM_K, niter=KM_NITER, seed=1234, trace=None):
     if nt == K:  # faiss's nx == k corner case: the points are the centroids, no iteration
         C = X[:K].copy()
         return C, np.argmax(_dots(X, C), axis=1).astype(np.int64)
-    C = _renorm(X[picks])
+    C = _renorm(X[picks])  # post_process_centroids precedes the iteration loop: also at niter = 0
     EPS = 1.0 / 1024.0
     prev, fixed = None, None
     for it in range(niter):

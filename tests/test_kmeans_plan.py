@@ -26,10 +26,7 @@ def _plan(n_tri, K, seed=1234):
     return buf.numpy().view(np.uint32)
 
 
-@pytest.mark.parametrize("n_tri,K,rows", [(6272, 20, [20, 21, 57, 5120, 5121, 5800, 6272]), (3000, 10, [10, 11, 2560,
-                                                                                                         2561, 3000])])
-def test_plan_matches_oracle(n_tri, K, rows):
-    p = _plan(n_tri, K)
+def _check_plan_rows(p, n_tri, K, rows):
     assert p[0] == 0x4B4D5031 and list(p[1:5]) == [n_tri, K, K * 256, L.N_RAND]
     init = p[p[5]:p[6]].view(np.uint16)
     cap, mw = K * 256, (n_tri + 31) // 32
@@ -45,6 +42,25 @@ def test_plan_matches_oracle(n_tri, K, rows):
             assert int(np.unpackbits(row.view(np.uint8)).sum()) == cap
     rnd = p[p[7]:p[7] + L.N_RAND].view(np.float32)
     assert np.array_equal(rnd, L.rand_floats(1234, L.N_RAND))
+
+
+@pytest.mark.parametrize("n_tri,K,rows", [(6272, 20, [20, 21, 57, 5120, 5121, 5800, 6272]), (3000, 10, [10, 11, 2560,
+                                                                                                         2561, 3000])])
+def test_plan_matches_oracle(n_tri, K, rows):
+    _check_plan_rows(_plan(n_tri, K), n_tri, K, rows)
+
+
+@pytest.mark.parametrize("K,rows", [(20, [5120, 5121, 16369, 16384]), (10, [2560, 2561, 16384])])
+def test_plan_rows_at_max_n_tri(K, rows):
+    """The plan of the largest launch (n_tri = 16384: 23 MB at K = 20, 28 MB at K = 10) at the
+    subsample cap, one past it, and the point counts whose chunk is KM_CHUNK_MAX = 1024 (nv >= 16369).
+    Built once per K (the build time is printed: 0.4-0.6 s on this project's CPUs, so no sharing
+    with the GPU tests beyond losses.kmeans_plan's own cache is needed)."""
+    import time
+    t0 = time.perf_counter()
+    p = _plan(16384, K)
+    print(f"ncn_kmeans_plan_fill(16384, {K}): {p.nbytes / 2 ** 20:.1f} MiB in {time.perf_counter() - t0:.2f} s")
+    _check_plan_rows(p, 16384, K, rows)
 
 
 def test_oracle_kmeans_subsamples_above_cap():
