@@ -270,6 +270,29 @@ struct FragsSigma : Frags<T> {
     }
 };
 constexpr int N_SIG32 = F_L3 + 4, N_SIG16 = 4;  // F_L1, F_L2, B_L1 / B_L2
+// The sigma pass's fragments with F_L1 and B_L1 (8 K=32 fragments, 32 VGPRs) held in registers for
+// the whole kernel (the indices are constants once the layer loops are unrolled): no LDS read in
+// front of 8 of a group's 14 MFMAs.  F_L2 and the four K=16 fragments stay in LDS: the pass has 128
+// VGPRs at two workgroups per CU, and the unrolled phase 2 (bwd_dw) needs the rest (with all ten
+// K=32 fragments in registers the fp16 pass spilled: DESIGN section 7, round 7 findings).
+template <typename T>
+struct FragsSigmaReg {
+    typename Mfma<T>::v8 r32[N_SIG32];  // (F_L2's two entries unused)
+    const typename Mfma<T>::v8* f32;
+    const typename Mfma<T>::v4* f16;
+    __device__ __forceinline__ void load(const FragsSigma<T>& F, int lane) {
+#pragma unroll
+        for (int f = 0; f < N_SIG32; f++)
+            if (f < F_L2 || f >= F_L3) r32[f] = F.f32[f * 64 + lane];
+        f32 = F.f32;
+        f16 = F.f16;
+    }
+    __device__ __forceinline__ typename Mfma<T>::v8 a32(int f, int lane) const {
+        if (f >= F_L2 && f < F_L3) return f32[f * 64 + lane];
+        return r32[f >= B_L1 ? f - (B_L1 - F_L3) : f];
+    }
+    __device__ __forceinline__ typename Mfma<T>::v4 a16(int f, int lane) const { return f16[(f - B_L2) * 64 + lane]; }
+};
 
 // Shared per-group forward (16 samples).  Produces every intermediate the backward needs.
 template <typename T>
@@ -787,6 +810,17 @@ __device__ __forceinline__ void bwd_dw(const uint16_t* X, int ng, int wid, int l
     constexpr bool RGB = (PART & BWD_RGB) != 0, SIG = (PART & BWD_SIGMA) != 0;
     if constexpr (PART == BWD_SIGMA) {  // 12 tiles: W1 (4 row x 2 col blocks) one per wave, W2 on waves 0-3
         constexpr int NX = x_count<PART>(), XO = x_origin<PART>();
+        if (ng == BWD_WAVES) {  // a full step, unrolled: its LDS reads can leave ahead of the MFMAs (same sequence)
+#pragma unroll
+            for (int q = 0; q < BWD_WAVES; q += 2) {
+                acc[0] = M::k32(x_pair<T, NX, XO>(X, q, BWD_WAVES, XA1 + (wid >> 1), lane),
+                                x_pair<T, NX, XO>(X, q, BWD_WAVES, XB1 + (wid & 1), lane), acc[0]);
+                if (wid < 4)
+                    acc[1] = M::k32(x_pair<T, NX, XO>(X, q, BWD_WAVES, XA2, lane),
+                                    x_pair<T, NX, XO>(X, q, BWD_WAVES, XB2 + wid, lane), acc[1]);
+            }
+            return;
+        }
         for (int q = 0; q < ng; q += 2) {
             acc[0] = M::k32(x_pair<T, NX, XO>(X, q, ng, XA1 + (wid >> 1), lane),
                             x_pair<T, NX, XO>(X, q, ng, XB1 + (wid & 1), lane), acc[0]);
@@ -923,8 +957,26 @@ __host__ __device__ inline int bwd_blocks_of(int64_t n) {
     return (int)(b < 1 ? 1 : (b > 256 ? 256 : b));
 }
 
+// Diagnostic build (tools/sigma_pass_probe.py): NCN_DIAG_SIGMA_TIMES records, per workgroup of the
+// sigma pass, wave 0's cycles summed over its steps — waiting on the prefetched loads, phase 1, the
+// first barrier, phase 2, the second barrier — the step count, and the realtime clock (100 MHz) at
+// the kernel's entry, before the first step, after the last and at the exit.
+#ifdef NCN_DIAG_SIGMA_TIMES
+__device__ unsigned long long ncn_sigma_times[512][10];
+#define SG_TNOW(v) const unsigned long long v = __builtin_readcyclecounter()
+#define SG_TADD(i, a, b) if (PART == BWD_SIGMA && threadIdx.x == 0 && blockIdx.x < 512) ncn_sigma_times[blockIdx.x][i] += (b) - (a)
+#define SG_TREAL(i) if (PART == BWD_SIGMA && threadIdx.x == 0 && blockIdx.x < 512) ncn_sigma_times[blockIdx.x][i] = __builtin_amdgcn_s_memrealtime()
+#define SG_TWAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+#else
+#define SG_TNOW(v)
+#define SG_TADD(i, a, b)
+#define SG_TREAL(i)
+#define SG_TWAIT()
+#endif
+
+// (the sigma pass runs two workgroups per CU: 4 waves per SIMD, so at most 128 VGPRs)
 template <typename T, int PART = BWD_ALL, bool DIN = false>
-__global__ __launch_bounds__(BWD_THREADS) void field_bwd_kernel(
+__global__ __launch_bounds__(BWD_THREADS, PART == BWD_SIGMA ? 4 : 2) void field_bwd_kernel(
     const float* __restrict__ dirs, int64_t n, const int32_t* __restrict__ n_dev, const uint16_t* __restrict__ wpacked,
     const typename Mfma<T>::v8* __restrict__ enc_cache, const float* __restrict__ dL_dsig,
     const float* __restrict__ dL_drgb, const float* __restrict__ loss_scale, float* __restrict__ dE_out,
@@ -971,6 +1023,19 @@ __global__ __launch_bounds__(BWD_THREADS) void field_bwd_kernel(
     __shared__ v8 F32s[NF32 * 64];
     __shared__ v4 F16s[NF16 * 64];
     __shared__ __attribute__((aligned(16))) uint16_t X[BWD_WAVES * NX * 256];  // dW operand images
+    SG_TREAL(6);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int64_t n_groups = (n + 15) / 16;
+    const int64_t stride = (int64_t)gridDim.x * BWD_WAVES;
+    int64_t base = (int64_t)blockIdx.x * BWD_WAVES;  // first group of this workgroup's step
+    BwdIn<T> nxt;
+    // (sigma pass: the first step's loads leave before the fragments are staged, so the two latencies
+    // overlap; the other passes keep their registers free until the loop)
+    if constexpr (SIGONLY) {
+        if (base + wid < n_groups)
+            bwd_load<T, PART>(nxt, base + wid, n, lane, enc_cache, dirs, dL_dsig, dL_dsig2, dL_drgb, stq, sth0, order, S,
+                              pos_src);
+    }
     {
         const v8* w32 = (const v8*)wpacked;
         const v4* w16 = (const v4*)(wpacked + N_FRAG32 * 512);
@@ -995,22 +1060,30 @@ __global__ __launch_bounds__(BWD_THREADS) void field_bwd_kernel(
             dL_ddirs[i] = 0.f;
     }
     __syncthreads();
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     float4_t acc[5];
 #pragma unroll
     for (int t = 0; t < 5; t++) acc[t] = zero4();
     float lm[4] = {0.f, 0.f, 0.f, 0.f};
-    const int64_t n_groups = (n + 15) / 16;
-    const int64_t stride = (int64_t)gridDim.x * BWD_WAVES;
-    int64_t base = (int64_t)blockIdx.x * BWD_WAVES;  // first group of this workgroup's step
-    BwdIn<T> nxt;
-    if (base + wid < n_groups)
-        bwd_load<T, PART>(nxt, base + wid, n, lane, enc_cache, dirs, dL_dsig, dL_dsig2, dL_drgb, stq, sth0, order, S,
-                          pos_src);
+    if constexpr (!SIGONLY) {
+        if (base + wid < n_groups)
+            bwd_load<T, PART>(nxt, base + wid, n, lane, enc_cache, dirs, dL_dsig, dL_dsig2, dL_drgb, stq, sth0, order, S,
+                              pos_src);
+    }
+    FragsSigmaReg<T> FR;  // (sigma pass) the K=32 fragments in registers for every group of the workgroup
+    if constexpr (SIGONLY) {
+        FragsSigma<T> Fl;
+        Fl.f32 = F32s;
+        Fl.f16 = F16s;
+        FR.load(Fl, lane);
+    }
+    SG_TREAL(7);
     for (; base < n_groups; base += stride) {
         const int64_t grp = base + wid;
         const int ng = (int)min<int64_t>(BWD_WAVES, n_groups - base);
         const BwdIn<T> cur = nxt;
+        SG_TNOW(g0);
+        SG_TWAIT();  // (diagnostic: this step's prefetched loads, and the last step's dE stores, have landed)
+        SG_TNOW(g1);
         if (grp + stride < n_groups)
             bwd_load<T, PART>(nxt, grp + stride, n, lane, enc_cache, dirs, dL_dsig, dL_dsig2, dL_drgb, stq, sth0, order,
                               S, pos_src);
@@ -1020,14 +1093,21 @@ __global__ __launch_bounds__(BWD_THREADS) void field_bwd_kernel(
                 float* po = pos_out + cls * 3 * pos_stride + 3 * sc_perm(grp * 16 + (lane & 15), cls);
                 po[0] = cur.px; po[1] = cur.py; po[2] = cur.pz;
             }
-            typename std::conditional<SIGONLY, FragsSigma<T>, Frags<T>>::type F;
-            const int z = opaque_zero();
-            F.f32 = F32s + z;
-            F.f16 = F16s + z;
-            bwd_group<T, PART, DIN>(F, X + wid * NX * 256, cur, grp, n, n_stride, lane, dE_pairs, lm, inv_S, stq, sth0,
-                                    &din);
+            if constexpr (SIGONLY) {
+                bwd_group<T, PART, DIN>(FR, X + wid * NX * 256, cur, grp, n, n_stride, lane, dE_pairs, lm, inv_S, stq,
+                                        sth0, &din);
+            } else {
+                Frags<T> F;
+                const int z = opaque_zero();
+                F.f32 = F32s + z;
+                F.f16 = F16s + z;
+                bwd_group<T, PART, DIN>(F, X + wid * NX * 256, cur, grp, n, n_stride, lane, dE_pairs, lm, inv_S, stq,
+                                        sth0, &din);
+            }
         }
+        SG_TNOW(g2);
         lds_barrier();  // (the dE stores and the next step's loads stay in flight)
+        SG_TNOW(g3);
         if constexpr (DIN) {
             // The transposed LDS reads of phase 2 must run with EXEC all ones (x_get): the group count
             // and the wave index are uniform, but this instantiation's register allocation keeps them
@@ -1036,8 +1116,17 @@ __global__ __launch_bounds__(BWD_THREADS) void field_bwd_kernel(
             bwd_dw<T, PART>(X, __builtin_amdgcn_readfirstlane(ng), __builtin_amdgcn_readfirstlane(wid), lane, acc);
         } else
             bwd_dw<T, PART>(X, ng, wid, lane, acc);
+        SG_TNOW(g4);
         lds_barrier();
+        SG_TNOW(g5);
+        SG_TADD(0, g0, g1);
+        SG_TADD(1, g1, g2);
+        SG_TADD(2, g2, g3);
+        SG_TADD(3, g3, g4);
+        SG_TADD(4, g4, g5);
+        SG_TADD(5, 0ull, 1ull);
     }
+    SG_TREAL(8);
     bwd_store_dw<PART>(slab + (int64_t)blockIdx.x * NCN_FIELD_NW, wid, lane, acc, inv_S);
     if constexpr (PART == BWD_RGB) return;  // (no encoding gradient in the rgb pass)
     // level maxima: the 16 lanes of a row (same g) share their 4 levels; the row leaders of the 8
@@ -1074,6 +1163,7 @@ __global__ __launch_bounds__(BWD_THREADS) void field_bwd_kernel(
     // a capped grid (ncn_field_bwd_mlp_part's n_blocks) leaves the scatter's remaining rows neutral
     if (PART == BWD_ALL && blockIdx.x == 0)
         for (int i = (int)gridDim.x * 16 + threadIdx.x; i < lm_rows * 16; i += BWD_THREADS) level_max[i] = 0.f;
+    SG_TREAL(9);
 }
 
 // Sum of the per-workgroup dW slabs: blockIdx.y takes a chunk of slabs (coalesced 1 KB rows),
@@ -2489,6 +2579,16 @@ int ncn_diag_sc_times(unsigned long long* host, int reset) {
         return (int)hipMemcpyToSymbol(HIP_SYMBOL(ncn_sc_times), zero, sizeof(zero));
     }
     return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(ncn_sc_times), 256 * 10 * sizeof(unsigned long long));
+}
+#endif
+
+#ifdef NCN_DIAG_SIGMA_TIMES
+int ncn_diag_sigma_times(unsigned long long* host, int reset) {
+    if (reset) {
+        static unsigned long long zero[512][10];
+        return (int)hipMemcpyToSymbol(HIP_SYMBOL(ncn_sigma_times), zero, sizeof(zero));
+    }
+    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(ncn_sigma_times), 512 * 10 * sizeof(unsigned long long));
 }
 #endif
 

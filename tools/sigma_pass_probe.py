@@ -65,3 +65,36 @@ assert part(1, 240) == 0
 print("samples", n, "rgb pass (240 workgroups) %.1f us" % ev_time(lambda: part(1, 240)), flush=True)
 for nb in (768, 512, 384, 256):
     print(f"sigma pass, {nb} workgroups: {ev_time(lambda: part(2, nb)):.1f} us", flush=True)
+
+# wave 0's cycles per step and phase, from the diagnostic build
+# (tools/build_field_variants.sh NCN_DIAG_SIGMA_TIMES)
+diag = os.environ.get("SIGMA_PROBE_DIAG_LIB", os.path.join(ROOT, "tools", "_build", "field_ncn_diag_sigma_times.so"))
+if os.path.exists(diag):
+    import ctypes  # noqa: E402
+    main = L
+    L = ctypes.CDLL(diag)
+    L.ncn_field_bwd_mlp_part.argtypes = _lib.SIGNATURES["ncn_field_bwd_mlp_part"]
+    L.ncn_field_bwd_mlp_part.restype = ctypes.c_int
+    print(f"diagnostic build, sigma pass, 512 workgroups: {ev_time(lambda: part(2, 512)):.1f} us", flush=True)
+    buf = (ctypes.c_ulonglong * (512 * 10))()
+    L.ncn_diag_sigma_times(buf, 1)
+    assert part(2, 512) == 0
+    torch.cuda.synchronize()
+    L.ncn_diag_sigma_times(buf, 0)
+    a = np.frombuffer(buf, dtype=np.uint64).reshape(512, 10).astype(np.float64)
+    # the workgroups' timeline on the 100 MHz realtime clock: entry, first step, last step's end, exit
+    t0 = a[:, 6].min()
+    pq = lambda v: " ".join(f"{x:.1f}" for x in np.percentile(v, [0, 10, 50, 90, 100]))  # noqa: E731
+    print(f"  kernel, first entry to last exit: {(a[:, 9].max() - t0) / 100:.1f} us; per workgroup (us; min p10 p50 p90 max):")
+    print(f"    entry {pq((a[:, 6] - t0) / 100)}")
+    print(f"    set-up (entry to the first step) {pq((a[:, 7] - a[:, 6]) / 100)}")
+    print(f"    steps {pq((a[:, 8] - a[:, 7]) / 100)}")
+    print(f"    end (slab rows, level maxima) {pq((a[:, 9] - a[:, 8]) / 100)}")
+    print(f"    exit {pq((a[:, 9] - t0) / 100)}")
+    steps = a[:, 5]
+    names = ["load wait", "phase 1", "barrier 1", "phase 2", "barrier 2"]
+    print(f"  steps per workgroup: {steps.min():.0f}-{steps.max():.0f}; wave 0's cycles per step (mean over workgroups):")
+    for i, nm in enumerate(names):
+        print(f"    {nm:10s} {(a[:, i] / steps).mean():8.0f}")
+    print(f"    {'total':10s} {(a[:, :5].sum(1) / steps).mean():8.0f}")
+    L = main
