@@ -204,10 +204,6 @@ __device__ __forceinline__ int opaque_zero() {
     return z;
 }
 
-// Workgroup barrier that orders LDS only: waits for the wave's own LDS operations (lgkmcnt) but
-// not for its outstanding global loads/stores/atomics (vmcnt), which __syncthreads() also drains.
-// For phases that exchange data through LDS while fire-and-forget global stores / atomics or
-// prefetch loads are in flight.
 // XCD-aware block order: workgroups are dispatched round-robin over the 8 XCDs (block b runs on
 // XCD b % 8), each with its own L2.  Renumbering blocks so that XCD x takes the contiguous logical
 // range [x * G/8, (x+1) * G/8) keeps neighbouring work — the samples of one ray patch, which
@@ -242,6 +238,10 @@ __device__ __forceinline__ void count_samples_wg(const int64_t* __restrict__ tot
     }
 }
 
+// Workgroup barrier that orders LDS only: waits for the wave's own LDS operations (lgkmcnt) but
+// not for its outstanding global loads/stores/atomics (vmcnt), which __syncthreads() also drains.
+// For phases that exchange data through LDS while fire-and-forget global stores / atomics or
+// prefetch loads are in flight.
 __device__ __forceinline__ void lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }

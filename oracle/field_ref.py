@@ -188,7 +188,7 @@ class _RoundST(torch.autograd.Function):
 
 class _RoundGrad(torch.autograd.Function):
     """Identity in the forward; in the backward the incoming gradient is rounded as the HIP field
-    backward rounds it (ncn_field_bwd, csrc/field.hip bwd_group): carried at the scale K = 128 * S
+    backward rounds it (ncn_field_bwd, csrc/field_bwd_mlp.h bwd_group): carried at the scale K = 128 * S
     (tcnn's fp16 module loss scale x the GradScaler's S), converted to the MLP operand type (fp16
     overflow -> inf, underflow -> subnormal / 0), and handed on unscaled: fp16(g K) / K."""
 
@@ -281,7 +281,7 @@ def field_forward_autograd(xyzs, dirs, P, levels, scale=0.5, emulate_f16=False, 
     emulation the forward operands are rounded where the HIP kernel rounds them (the rounding is
     straight-through in the backward), so ReLU masks match the kernel's.  impl: the encoding's
     statement ("torch" or "c", see encode()).
-    bwd_scale (with emulate): the backward's gradients are rounded where csrc/field.hip's bwd_group
+    bwd_scale (with emulate): the backward's gradients are rounded where csrc/field_bwd_mlp.h's bwd_group
     rounds them, at that scale (128 x the GradScaler's scale; 1 for bf16): the pre-sigmoid output
     gradient (dY5), the pre-ReLU gradients of layers 4, 3 and 1 (dD4, dD3, dD1), dL/dh after the rgb
     path and TruncExp's term are added (dhh), and dL/denc — the fp32 product of those rounded

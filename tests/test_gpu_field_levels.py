@@ -24,7 +24,7 @@
    level-split density mode 2 equal to mode 1 bit for bit, ncn_field_sort_windows against the host's
    clipped Morton keys.
 
-4. Finding (fixed in csrc/field.hip sc_push_run): the cell key of (2047, 2047, 1023) equalled the LDS
+4. Finding (fixed in csrc/field_scatter.h sc_push_run): the cell key of (2047, 2047, 1023) equalled the LDS
    table's empty marker; test_scatter_cell_whose_key_is_the_empty_marker is its regression.
 
 Measured (profiles/round7/field_levels_test.log), worst over the cases, next to the bound:
@@ -125,7 +125,7 @@ def _mlp_pass(m, x, d, dsig, drgb, n_dev=None, order=None, ws=None):
 
 
 def _decode(ws, n, precision):
-    """The workspace as the scatter reads it (csrc/field.hip field_bwd_kernel / ScDE): a header of 4
+    """The workspace as the scatter reads it (csrc/field_de_ws.h; field_bwd_mlp.h field_bwd_kernel / field_scatter.h ScDE): a header of 4
     floats {1 / S, operand type, class mask, -}, then [16][n_stride] pairs of the operand type,
     n_stride = (n + 3) & ~3; the pairs times 1 / S (a power of two: exact).
     -> (header (4,) f32, dE (n, 32) f32 level-major pairs, the padding pairs (16, n_stride - n, 2))."""

@@ -2,7 +2,7 @@
 what the GPU test (tests/test_gpu_field_levels.py) holds the MLP pass's dE to.
 
 (a) The reference's own error stays inside the cap: the emulating oracle (operands rounded where
-    csrc/field.hip rounds them, forward and backward) run with fp32 tensors against the same run with
+    csrc/field_mlp.h and field_bwd_mlp.h round them, forward and backward) run with fp32 tensors against the same run with
     every tensor in fp64 — the same operand rounding points, only the accumulation differs (the
     positions too: the encoding's weights then differ in their last bit, and most of the share comes
     from operands that this flips; with fp32 positions it is 0.03 % / 0.02 %).  Every level's outlier

@@ -1,5 +1,6 @@
 #!/bin/bash
-# Diagnostic builds of csrc/field.hip with parts of the backward compiled out (tools/field_probe.py).
+# Diagnostic builds of csrc/field.hip (one unit: the field_*.h headers; the switches are in field_diag.h and
+# field_de_ws.h) with parts of the backward compiled out (tools/field_probe.py).
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p tools/_build

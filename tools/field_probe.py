@@ -1,6 +1,6 @@
 """Diagnostic: time ncn_field_bwd / ncn_field_fwd variants on realistic marched samples.
 
-Variants are diagnostic builds of csrc/field.hip (tools/build_field_variants.sh) with parts of the
+Variants are diagnostic builds of csrc/field.hip and its field_*.h headers (tools/build_field_variants.sh) with parts of the
 backward compiled out, to attribute the kernel time.  Not part of the product."""
 import ctypes
 import glob
