@@ -3,16 +3,14 @@
 //  * faiss.Kmeans(3, K, niter, spherical=True) for any number of points: the random draws on the
 //    host (ncn_kmeans_draws), the Lloyd rounds over the <= 256 K training points in ONE workgroup
 //    (ncn_kmeans_train) and the final search of every point as a streaming pass (ncn_kmeans_assign).
-// The algorithm and its arithmetic are oracle/losses_ref.py:spherical_kmeans (as the training
-// step's clustering kernel in loss.hip, whose small helpers are restated here).  Nothing in this
-// file waits on another workgroup.
+// The algorithm is oracle/losses_ref.py:spherical_kmeans; its arithmetic, constants and draws are
+// those of kmeans_faiss.h, shared with the training step's clustering kernel (loss.hip).  Nothing
+// in this file waits on another workgroup.
 #pragma clang fp contract(off)
 
-#include <algorithm>
 #include <cstring>
-#include <random>
-#include <unordered_map>
 #include "common.h"
+#include "kmeans_faiss.h"
 #include "../../include/ncnerf.h"
 
 namespace ncn {
@@ -57,47 +55,17 @@ __global__ __launch_bounds__(256) void depth_normals_image_kernel(const float* _
 
 // ---- k-means ----
 constexpr int KF_MAX_K = 32;
-constexpr int KF_MAX_PTS = 256;     // faiss ClusteringParameters::max_points_per_centroid
 constexpr int KF_MAX_NITER = 64;
-constexpr int KF_N_RAND = 4096;     // split_clusters' random floats handed to the kernel
 constexpr int KF_THREADS = 1024;    // the training workgroup
-constexpr int KF_PER_THREAD = KF_MAX_K * KF_MAX_PTS / KF_THREADS;  // 8 points in registers
+constexpr int KF_PER_THREAD = KF_MAX_K * FAISS_MAX_PTS / KF_THREADS;  // 8 points in registers
 constexpr int KF_COPIES = 8;        // copies of the LDS accumulators (thread t adds into copy t % 8)
-constexpr double KF_FXL = 549755813888.0;  // 2^39: the fixed point of the Lloyd sums
-
-// argmax_k <x, C_k> with ((x0 c0 + x1 c1) + x2 c2) in f32, no FMA (contract(off) above); ties ->
-// lowest k (a NaN point compares false everywhere and stays at 0).
-__device__ __forceinline__ int nearest_k(const float (*C)[3], int K, float x, float y, float z) {
-    int best = 0;
-    float bv = x * C[0][0] + y * C[0][1] + z * C[0][2];
-    for (int k = 1; k < K; k++) {
-        const float v = x * C[k][0] + y * C[k][1] + z * C[k][2];
-        if (v > bv) { bv = v; best = k; }
-    }
-    return best;
-}
-
-__device__ __forceinline__ unsigned long long kf_fix(float v) {
-    return (unsigned long long)__double2ll_rn((double)v * KF_FXL);
-}
-
-// faiss fvec_renorm_L2 of one 3-vector: x *= (float)(1.0 / sqrtf(|x|^2)) when |x|^2 > 0
-__device__ __forceinline__ void kf_renorm3(float* x) {
-    const float nr = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
-    if (nr > 0.f) {
-        const float inv = (float)(1.0 / (double)sqrtf(nr));
-        x[0] *= inv; x[1] *= inv; x[2] *= inv;
-    }
-}
 
 // faiss Clustering::train on the (already subsampled) training set, one workgroup: thread t holds
 // points t, t + 1024, ... in registers; centroids, the exact int64 sums (x, y, z at 2^-39, count)
-// and the round's means live in LDS.  Per round: search (nearest_k) + LDS integer atomics, mean =
-// sum * (1 / count), split_clusters serially in thread 0 (each empty cluster ci, in order, takes
-// the cluster cj found by walking cj = 0, 1, ... (mod K) until rand_float() < (count_cj - 1) /
-// (nt - K), the floats restarting at rnd[0] every round; +-1/1024 perturbation; counts halve as
-// floats), L2 renormalisation.  nt == K is faiss's corner case: the points are the centroids.
-// A split walk that runs past the KF_N_RAND floats has left the restated algorithm: the centroids
+// and the round's means live in LDS.  Per round: search (faiss_nearest_step) + LDS integer atomics,
+// mean = sum * (1 / count), faiss_split_clusters serially in thread 0, L2 renormalisation.
+// nt == K is faiss's corner case: the points are the centroids.
+// A split walk that runs past the FAISS_N_RAND floats has left the restated algorithm: the centroids
 // are then written as NaN (never a value computed from different draws).
 __global__ __launch_bounds__(KF_THREADS) void kmeans_train_kernel(const float* __restrict__ pts, int nt, int K,
                                                                   int niter, const int64_t* __restrict__ init_idx,
@@ -125,7 +93,7 @@ __global__ __launch_bounds__(KF_THREADS) void kmeans_train_kernel(const float* _
     if (t < K) {
         const int64_t s = init_idx[t];
         float c[3] = {pts[3 * s], pts[3 * s + 1], pts[3 * s + 2]};
-        kf_renorm3(c);
+        faiss_renorm3(c);
         C[t][0] = c[0]; C[t][1] = c[1]; C[t][2] = c[2];
     }
     if (t == 0) overrun = 0;
@@ -134,34 +102,30 @@ __global__ __launch_bounds__(KF_THREADS) void kmeans_train_kernel(const float* _
         for (int q = t; q < KF_COPIES * KF_MAX_K * 4; q += KF_THREADS) accf[q] = 0ull;
         __syncthreads();
         unsigned long long(*my)[4] = acc[t & (KF_COPIES - 1)];
-        // nearest_k for the thread's 8 points at once, clusters outermost: each centroid is read
-        // from LDS once per thread and round (the same products, sums and comparisons in the same
-        // cluster order per point)
+        // faiss_nearest for the thread's 8 points at once, clusters outermost: each centroid is read
+        // from LDS once per thread and round (the same steps in the same cluster order per point)
         int best[KF_PER_THREAD];
         float bv[KF_PER_THREAD];
         {
-            const float c0 = C[0][0], c1 = C[0][1], c2 = C[0][2];
+            const float c[3] = {C[0][0], C[0][1], C[0][2]};
 #pragma unroll
             for (int j = 0; j < KF_PER_THREAD; j++) {
-                bv[j] = px[j] * c0 + py[j] * c1 + pz[j] * c2;
+                bv[j] = faiss_dot3(c, px[j], py[j], pz[j]);
                 best[j] = 0;
             }
         }
         for (int k = 1; k < K; k++) {
-            const float c0 = C[k][0], c1 = C[k][1], c2 = C[k][2];
+            const float c[3] = {C[k][0], C[k][1], C[k][2]};
 #pragma unroll
-            for (int j = 0; j < KF_PER_THREAD; j++) {
-                const float v = px[j] * c0 + py[j] * c1 + pz[j] * c2;
-                if (v > bv[j]) { bv[j] = v; best[j] = k; }
-            }
+            for (int j = 0; j < KF_PER_THREAD; j++) faiss_nearest_step(c, k, px[j], py[j], pz[j], bv[j], best[j]);
         }
 #pragma unroll
         for (int j = 0; j < KF_PER_THREAD; j++) {
             if (t + j * KF_THREADS < nt) {
                 const int a = best[j];
-                atomicAdd(&my[a][0], kf_fix(px[j]));
-                atomicAdd(&my[a][1], kf_fix(py[j]));
-                atomicAdd(&my[a][2], kf_fix(pz[j]));
+                atomicAdd(&my[a][0], faiss_fix(px[j]));
+                atomicAdd(&my[a][1], faiss_fix(py[j]));
+                atomicAdd(&my[a][2], faiss_fix(pz[j]));
                 atomicAdd(&my[a][3], 1ull);
             }
         }
@@ -178,36 +142,16 @@ __global__ __launch_bounds__(KF_THREADS) void kmeans_train_kernel(const float* _
             if (c == 3) {
                 cnt[k] = n;
             } else {
-                const float s = (float)((double)q * (1.0 / KF_FXL));
+                const float s = (float)((double)q * (1.0 / FAISS_FXL));
                 nc[k][c] = n > 0.f ? s * (1.0f / n) : 0.f;
             }
         }
         __syncthreads();
-        if (t == 0) {
-            const float EPS = 1.0f / 1024.0f;
-            const double denom = (double)(float)(nt - K);
-            int ri = 0;
-            for (int ci = 0; ci < K; ci++) {
-                if (cnt[ci] != 0.f) continue;
-                int cj = 0;
-                for (;; cj = (cj + 1) % K) {
-                    const float pr = (float)(((double)cnt[cj] - 1.0) / denom);
-                    if (ri >= KF_N_RAND) { overrun = 1; break; }
-                    if (rnd[ri++] < pr) break;
-                }
-                for (int q = 0; q < 3; q++) {
-                    nc[ci][q] = nc[cj][q];
-                    if (q % 2 == 0) { nc[ci][q] *= 1 + EPS; nc[cj][q] *= 1 - EPS; }
-                    else { nc[ci][q] *= 1 - EPS; nc[cj][q] *= 1 + EPS; }
-                }
-                cnt[ci] = cnt[cj] / 2;
-                cnt[cj] -= cnt[ci];
-            }
-        }
+        if (t == 0 && faiss_split_clusters(nc, cnt, K, nt, rnd, FAISS_N_RAND)) overrun = 1;
         __syncthreads();
         if (t < K) {
             float c[3] = {nc[t][0], nc[t][1], nc[t][2]};
-            kf_renorm3(c);
+            faiss_renorm3(c);
             C[t][0] = c[0]; C[t][1] = c[1]; C[t][2] = c[2];
         }
         __syncthreads();
@@ -239,7 +183,7 @@ __global__ __launch_bounds__(KA_THREADS) void kmeans_assign_kernel(const float* 
     __syncthreads();
     const int64_t stride = (int64_t)gridDim.x * KA_THREADS;
     for (int64_t i = (int64_t)blockIdx.x * KA_THREADS + t; i < n; i += stride) {
-        const int a = nearest_k(C, K, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]);
+        const int a = faiss_nearest(C, K, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]);
         assign[i] = a;
         atomicAdd(&hist[a], 1ull);
     }
@@ -250,27 +194,6 @@ __global__ __launch_bounds__(KA_THREADS) void kmeans_assign_kernel(const float* 
 }  // namespace ncn
 
 using namespace ncn;
-
-// faiss rand_perm(perm, n, seed) (utils/random.cpp) for its first m steps, the first m entries:
-// Fisher-Yates with RandomGenerator::rand_int(max) = mt() % max over std::mt19937((unsigned)seed).
-// Only the entries a swap touched are stored (<= 2 m), so n may be in the hundreds of millions.
-static void kf_rand_perm_prefix(int64_t n, uint32_t seed, int64_t m, int64_t* out) {
-    std::unordered_map<int64_t, int64_t> moved;
-    moved.reserve((size_t)(2 * m));
-    auto at = [&](int64_t i) {
-        auto f = moved.find(i);
-        return f == moved.end() ? i : f->second;
-    };
-    std::mt19937 mt(seed);
-    const int64_t steps = std::min(m, n - 1);
-    for (int64_t i = 0; i < steps; i++) {
-        const int64_t i2 = i + (int64_t)(mt() % (uint32_t)(n - i));
-        const int64_t vi = at(i), v2 = at(i2);
-        moved[i] = v2;
-        moved[i2] = vi;
-    }
-    for (int64_t i = 0; i < m; i++) out[i] = at(i);
-}
 
 extern "C" {
 
@@ -291,14 +214,15 @@ int ncn_kmeans_draws(int64_t nx, int K, uint32_t seed, int64_t* sub_idx, int64_t
                 "ncn_kmeans_draws: bad arguments (K = %d, at most %d)", K, KF_MAX_K);
     NCN_REQUIRE(nx >= K, hipErrorInvalidValue, "ncn_kmeans_draws: %lld points for %d clusters", (long long)nx, K);
     NCN_REQUIRE(nx <= 0x7FFFFFFF, hipErrorInvalidValue, "ncn_kmeans_draws: faiss's rand_perm takes an int count");
-    const int64_t cap = (int64_t)K * KF_MAX_PTS, nt = std::min(nx, cap);
+    const int64_t cap = (int64_t)K * FAISS_MAX_PTS, nt = std::min(nx, cap);
+    std::vector<int32_t> scratch;
     if (nx > cap) {
-        kf_rand_perm_prefix(nx, seed, cap, sub_idx);  // subsample_training_set
+        faiss_rand_perm_prefix(nx, seed, cap, sub_idx, scratch);  // subsample_training_set
     } else {
         for (int64_t i = 0; i < nt; i++) sub_idx[i] = i;
     }
     int64_t picks[KF_MAX_K];
-    kf_rand_perm_prefix(nt, seed + 1, K, picks);  // init, redo 0: seed + 1 + 0 * 15486557
+    faiss_rand_perm_prefix(nt, seed + 1, K, picks, scratch);  // init, redo 0: seed + 1 + 0 * 15486557
     for (int k = 0; k < K; k++) {
         init_idx[k] = sub_idx[picks[k]];
         if (init_rows != nullptr) init_rows[k] = picks[k];
@@ -308,15 +232,14 @@ int ncn_kmeans_draws(int64_t nx, int K, uint32_t seed, int64_t* sub_idx, int64_t
 
 int ncn_kmeans_rand_floats(uint32_t seed, int n, float* host_out) {
     NCN_REQUIRE(host_out != nullptr && n >= 0, hipErrorInvalidValue, "ncn_kmeans_rand_floats: bad arguments");
-    std::mt19937 mt(seed);  // RandomGenerator::rand_float() = mt() / float(mt.max())
-    for (int i = 0; i < n; i++) host_out[i] = (float)mt() / (float)mt.max();
+    faiss_rand_floats(seed, n, host_out);
     return 0;
 }
 
 int ncn_kmeans_train(const float* train_pts, int nt, int K, int niter, const int64_t* init_idx,
                      const float* rand_floats, float* centroids, void* stream) {
     NCN_REQUIRE(K > 0 && K <= KF_MAX_K, hipErrorInvalidValue, "ncn_kmeans_train: K = %d (1..%d)", K, KF_MAX_K);
-    NCN_REQUIRE(nt >= K && nt <= K * KF_MAX_PTS, hipErrorInvalidValue,
+    NCN_REQUIRE(nt >= K && nt <= K * FAISS_MAX_PTS, hipErrorInvalidValue,
                 "ncn_kmeans_train: %d training points for K = %d (K..256 K; subsample with ncn_kmeans_draws)", nt, K);
     NCN_REQUIRE(niter >= 0 && niter <= KF_MAX_NITER, hipErrorInvalidValue, "ncn_kmeans_train: niter = %d (0..%d)", niter,
                 KF_MAX_NITER);

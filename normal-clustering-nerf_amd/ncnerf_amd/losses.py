@@ -32,6 +32,7 @@ from . import _lib, vren
 from ._lib import call, check_input
 
 N_OUT = 11  # ncn_cluster_loss out_losses
+K_CLUSTERS, K_ITERS = 20, 20  # losses.py:86-89: faiss.Kmeans(3, 20, niter=20)
 _WS = {}
 
 
@@ -62,6 +63,21 @@ def kmeans_plan(dev, n_tri, K, seed=1234):
         plan = host.to(dev)
         _PLANS[key] = plan
     return plan
+
+
+def cluster_launch(normals, K, niter, seed, t_sim, w, w_dev=None, step_dev=None, sched=(0.0, 1.0), photo=None):
+    """The one ncn_cluster_loss launch on (T, 3) normals: allocates its outputs and fetches the
+    (device, K) workspace and the (T, K, seed) plan.  w: host weights, overridden by the device
+    weights w_dev; step_dev + sched = (start, grow): the weight schedule on the device; photo: the
+    photometric terms for the loss total.  -> raw (N_OUT), labels (T), centroids (K, 3), dn (3, T, 3)."""
+    T, dev = normals.shape[0], normals.device
+    out = torch.empty(N_OUT, dtype=torch.float32, device=dev)
+    labels = torch.empty(T, dtype=torch.int32, device=dev)
+    cents = torch.empty(K, 3, dtype=torch.float32, device=dev)
+    dn = torch.empty(3, T, 3, dtype=torch.float32, device=dev)
+    call("ncn_cluster_loss", normals, T, K, niter, kmeans_plan(dev, T, K, seed), t_sim, w[0], w[1], w[2], w_dev,
+         step_dev, sched[0], sched[1], photo, out, labels, cents, dn, _cluster_workspace(dev, K))
+    return out, labels, cents, dn
 
 
 def check_cluster_status(dev=None):
@@ -106,15 +122,18 @@ class _Normals(torch.autograd.Function):
         return None, None, ddepth, None, None, None
 
 
-def extract_normals_from_ray_batch(rays_o, rays_d, depth, x123_idx):
-    """Drop-in for datasets/hypersim_src/utils.py:_extract_normals_from_ray_batch (fp32)."""
-    f = lambda t: t.float().contiguous()
-    idx = lambda t: t.long().contiguous()
+def _ray_args(rays_o, rays_d, depth, x123_idx):
+    """The normals nodes' tensor arguments: fp32 / int64, contiguous, on the GPU."""
     for t, n in ((rays_o, "rays_o"), (rays_d, "rays_d"), (depth, "depth")):
         if not t.is_cuda:
             raise RuntimeError(f"{n} must be a CUDA tensor")
-    return _Normals.apply(f(rays_o), f(rays_d), f(depth), idx(x123_idx["x1"]), idx(x123_idx["x2"]),
-                          idx(x123_idx["x3"]))
+    return tuple(t.float().contiguous() for t in (rays_o, rays_d, depth)) + tuple(
+        x123_idx[k].long().contiguous() for k in ("x1", "x2", "x3"))
+
+
+def extract_normals_from_ray_batch(rays_o, rays_d, depth, x123_idx):
+    """Drop-in for datasets/hypersim_src/utils.py:_extract_normals_from_ray_batch (fp32)."""
+    return _Normals.apply(*_ray_args(rays_o, rays_d, depth, x123_idx))
 
 
 class _ClusterLoss(torch.autograd.Function):
@@ -123,16 +142,7 @@ class _ClusterLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, normals, K, niter, seed, t_sim, w):
-        T = normals.shape[0]
-        dev = normals.device
-        out = torch.empty(N_OUT, dtype=torch.float32, device=dev)
-        labels = torch.empty(T, dtype=torch.int32, device=dev)
-        cents = torch.empty(K, 3, dtype=torch.float32, device=dev)
-        dn = torch.empty(3, T, 3, dtype=torch.float32, device=dev)
-        ws = _cluster_workspace(dev, K)
-        hw, w_dev = _split_weights(w)
-        call("ncn_cluster_loss", normals, T, K, niter, kmeans_plan(dev, T, K, seed), t_sim, hw[0], hw[1], hw[2], w_dev,
-             None, 0.0, 1.0, None, out, labels, cents, dn, ws)
+        out, labels, cents, dn = cluster_launch(normals, K, niter, seed, t_sim, *_split_weights(w))
         ctx.save_for_backward(dn)
         terms = out[4:7].clone()
         ctx.mark_non_differentiable(labels, cents, out)
@@ -159,7 +169,7 @@ def _weights_arg(w):
     return w if isinstance(w, torch.Tensor) else tuple(float(x) for x in w)
 
 
-def cluster_losses(norm_depth, K=20, niter=20, seed=1234, t_similar=0.99, w=(1.0, 1.0, 1.0)):
+def cluster_losses(norm_depth, K=K_CLUSTERS, niter=K_ITERS, seed=1234, t_similar=0.99, w=(1.0, 1.0, 1.0)):
     """Weighted (ort, centr_dot, centr_L1) terms, labels (+-1..3, 0, -9 invalid), centroids, raw stats."""
     check_input(norm_depth, "norm_depth")
     return _ClusterLoss.apply(norm_depth, K, niter, seed, t_similar, _weights_arg(w))
@@ -186,14 +196,7 @@ class _NormalsClusterLoss(torch.autograd.Function):
         dev = depth.device
         normals = torch.empty(T, 3, dtype=torch.float32, device=dev)
         call("ncn_normals_fwd", rays_o, rays_d, depth, x1, x2, x3, T, normals)
-        out = torch.empty(N_OUT, dtype=torch.float32, device=dev)
-        labels = torch.empty(T, dtype=torch.int32, device=dev)
-        cents = torch.empty(K, 3, dtype=torch.float32, device=dev)
-        dn = torch.empty(3, T, 3, dtype=torch.float32, device=dev)
-        ws = _cluster_workspace(dev, K)
-        hw, w_dev = _split_weights(w)
-        call("ncn_cluster_loss", normals, T, K, niter, kmeans_plan(dev, T, K, seed), t_sim, hw[0], hw[1], hw[2], w_dev,
-             None, 0.0, 1.0, None, out, labels, cents, dn, ws)
+        out, labels, cents, dn = cluster_launch(normals, K, niter, seed, t_sim, *_split_weights(w))
         ctx.save_for_backward(rays_o, rays_d, depth, x1, x2, x3, dn)
         terms = out[4:7].clone()
         ctx.mark_non_differentiable(normals, labels, cents, out)
@@ -209,16 +212,11 @@ class _NormalsClusterLoss(torch.autograd.Function):
         return None, None, ddepth, None, None, None, None, None, None, None, None
 
 
-def normals_cluster_losses(rays_o, rays_d, depth, x123_idx, K=20, niter=20, seed=1234, t_similar=0.99,
+def normals_cluster_losses(rays_o, rays_d, depth, x123_idx, K=K_CLUSTERS, niter=K_ITERS, seed=1234, t_similar=0.99,
                            w=(1.0, 1.0, 1.0)):
     """extract_normals_from_ray_batch + cluster_losses fused: (terms, normals, labels, centroids, raw)."""
-    f = lambda t: t.float().contiguous()
-    idx = lambda t: t.long().contiguous()
-    for t, n in ((rays_o, "rays_o"), (rays_d, "rays_d"), (depth, "depth")):
-        if not t.is_cuda:
-            raise RuntimeError(f"{n} must be a CUDA tensor")
-    return _NormalsClusterLoss.apply(f(rays_o), f(rays_d), f(depth), idx(x123_idx["x1"]), idx(x123_idx["x2"]),
-                                     idx(x123_idx["x3"]), K, niter, seed, t_similar, _weights_arg(w))
+    return _NormalsClusterLoss.apply(*_ray_args(rays_o, rays_d, depth, x123_idx), K, niter, seed, t_similar,
+                                     _weights_arg(w))
 
 
 class _PhotoLoss(torch.autograd.Function):
@@ -278,13 +276,7 @@ class _NeRFLossFused(torch.autograd.Function):
         call("ncn_photo_normals_count_fwd", rgb, rgb_gt, opacity, R, w_op, photo, rays_o, rays_d, depth, x1, x2, x3, T,
              normals, tot, tot.shape[0] if tot is not None else 0, cj.counter if cj else None, cj.out if cj else None,
              cj.acc if cj else None)
-        out = torch.empty(N_OUT, dtype=torch.float32, device=dev)
-        labels = torch.empty(T, dtype=torch.int32, device=dev)
-        cents = torch.empty(K, 3, dtype=torch.float32, device=dev)
-        dn = torch.empty(3, T, 3, dtype=torch.float32, device=dev)
-        ws = _cluster_workspace(dev, K)
-        call("ncn_cluster_loss", normals, T, K, niter, kmeans_plan(dev, T, K, seed), t_sim, w[0], w[1], w[2], None,
-             step_dev, sched[0], sched[1], photo, out, labels, cents, dn, ws)
+        out, labels, cents, dn = cluster_launch(normals, K, niter, seed, t_sim, w, None, step_dev, sched, photo)
         ctx.save_for_backward(rgb, opacity, depth, rays_o, rays_d, rgb_gt, photo, dn)
         ctx.w_op = w_op
         ctx.set_materialize_grads(False)
@@ -401,6 +393,37 @@ class NeRFMTLoss(nn.Module):
             return torch.tensor(0.0, device=dev)
         return torch.where(torch.isfinite(loss), loss, torch.zeros_like(loss))
 
+    @property
+    def clustering(self):
+        return self.norm_D_C_ort_dot_w > 0 or self.norm_D_C_centr_dot_w > 0 or self.norm_D_C_centr_L1_w > 0
+
+    def reference_config(self, n_rays, n_opacity, patch_area, off, rays_grad):
+        """Is this the reference configuration the fused node (_NeRFLossFused) serves?  The loss's own
+        settings (rgb + opacity + clustering terms on patch-sampled depth normals, nothing else) plus
+        the batch facts: n_rays supervised rays that are all the rendered ones (n_opacity), whole
+        64-ray patches with the standard 8x8 offsets `off`, no ray gradients (pose refinement)."""
+        return (not rays_grad and self.clustering and self.pred_norm_depth and not self.random_tr_poses
+                and self.opacity_w > 0 and self.distortion_w == 0
+                and self.ray_sampling_strategy in ("all_images_triang_patch", "same_image_triang_patch")
+                and self.depth_w == 0 and self.norm_DEpth_L1_w == 0 and self.norm_DEpth_dot_w == 0
+                and self.reg_depth_w == 0 and n_rays == n_opacity and n_rays % 64 == 0 and n_rays > 0
+                and _standard_patch_offsets(patch_area, off))
+
+    def patch_triang_idx(self, seq_len, patch_s, off, dev):
+        """Ray indices x1/x2/x3 of the patch triangles (losses.py:307-313); constant for a given
+        (batch, patch, offsets): cached so the step issues no H2D copies."""
+        key = (seq_len, int(patch_s), str(dev)) + tuple(_offsets_key(off[k]) for k in ("x1", "x2", "x3"))
+        hit = None if None in key else self._idx_cache.get(key)
+        if hit is None:
+            pix = einops.rearrange(torch.arange(0, seq_len, device=dev), "(n s) -> n s", s=patch_s)
+            hit = {k: einops.rearrange(pix[:, torch.as_tensor(off[k], device=dev)], "n s -> (n s)").contiguous()
+                   for k in ("x1", "x2", "x3")}
+            if None not in key:
+                if len(self._idx_cache) > 16:
+                    self._idx_cache.clear()
+                self._idx_cache[key] = hit
+        return hit
+
     def _fused(self, pred_w_gt, target_gt, pred_unsup, kwargs):
         """The reference configuration in one autograd node (_NeRFLossFused)."""
         f = lambda t: t.float().contiguous()
@@ -422,8 +445,8 @@ class NeRFMTLoss(nn.Module):
                 raise RuntimeError(f"{n} must be a CUDA tensor")
         total, l_rgb, l_op, ort, cdot, cl1, labels, cents, raw, normals = _NeRFLossFused.apply(
             f(pred_w_gt["rgb"]), f(pred_unsup["opacity"]), f(pred_unsup["depth"]), f(pred_unsup["rays_o"]),
-            f(pred_unsup["rays_d"]), f(target_gt["rgb"]), x["x1"], x["x2"], x["x3"], float(self.opacity_w), 20, 20,
-            self.kmeans_seed, 1.0 - self.norm_CAN_tres, w, step_dev, (float(self.can_sched_start), float(self._grow)),
+            f(pred_unsup["rays_d"]), f(target_gt["rgb"]), x["x1"], x["x2"], x["x3"], float(self.opacity_w), K_CLUSTERS,
+            K_ITERS, self.kmeans_seed, 1.0 - self.norm_CAN_tres, w, step_dev, (float(self.can_sched_start), float(self._grow)),
             kwargs.get("count_job"))
         self.last_cluster = (labels, cents, raw)
         self.last_normals = normals  # the patch triangles' normals (zero / invalid ones included)
@@ -455,38 +478,21 @@ class NeRFMTLoss(nn.Module):
             pix = einops.rearrange(torch.arange(0, seq_len, device=dev), "(n s) -> n s", s=3)
             return {"x1": pix[:, 0], "x2": pix[:, 1], "x3": pix[:, 2]}
 
-        def get_patch_triang_idx(seq_len, patch_s, off):
-            # constant for a given (batch, patch, offsets): cached so the step issues no H2D copies
-            key = (seq_len, int(patch_s), str(dev)) + tuple(_offsets_key(off[k]) for k in ("x1", "x2", "x3"))
-            hit = None if None in key else self._idx_cache.get(key)
-            if hit is None:
-                pix = einops.rearrange(torch.arange(0, seq_len, device=dev), "(n s) -> n s", s=patch_s)
-                hit = {k: einops.rearrange(pix[:, torch.as_tensor(off[k], device=dev)], "n s -> (n s)").contiguous()
-                       for k in ("x1", "x2", "x3")}
-                if None not in key:
-                    if len(self._idx_cache) > 16:
-                        self._idx_cache.clear()
-                    self._idx_cache[key] = hit
-            return hit
-
         n_unsup, n_w_gt = pred_unsup["depth"].shape[0], pred_w_gt["rgb"].shape[0]
+        off = None
         if self.ray_sampling_strategy in ["all_images_triang", "same_image_triang"]:
             pred_w_gt["x123_idx"] = get_triang_idx(n_w_gt)
             pred_unsup["x123_idx"] = get_triang_idx(n_unsup)
         elif self.ray_sampling_strategy in ["all_images_triang_patch", "same_image_triang_patch"]:
             off = {"x1": target_raw["x1_offsets_local"], "x2": target_raw["x2_offsets_local"],
                    "x3": target_raw["x3_offsets_local"]}
-            pred_w_gt["x123_idx"] = get_patch_triang_idx(n_w_gt, target_raw["patch_area"], off)
-            pred_unsup["x123_idx"] = get_patch_triang_idx(n_unsup, target_raw["patch_area"], off)
-        clustering = self.norm_D_C_ort_dot_w > 0 or self.norm_D_C_centr_dot_w > 0 or self.norm_D_C_centr_L1_w > 0
+            pred_w_gt["x123_idx"] = self.patch_triang_idx(n_w_gt, target_raw["patch_area"], off, dev)
+            pred_unsup["x123_idx"] = self.patch_triang_idx(n_unsup, target_raw["patch_area"], off, dev)
+        clustering = self.clustering
         # pose refinement (the rays require grad): the unfused _Normals + cluster_losses branch, whose
         # backward reaches the rays; the fused nodes stop at the depth
         rays_grad = torch.is_grad_enabled() and (pred_raw["rays_o"].requires_grad or pred_raw["rays_d"].requires_grad)
-        if (not rays_grad and clustering and self.pred_norm_depth and unsup_start == 0 and self.opacity_w > 0 and self.distortion_w == 0
-                and self.ray_sampling_strategy in ("all_images_triang_patch", "same_image_triang_patch")
-                and self.depth_w == 0 and self.norm_DEpth_L1_w == 0 and self.norm_DEpth_dot_w == 0
-                and self.reg_depth_w == 0 and n_w_gt == pred_unsup["opacity"].shape[0] and n_w_gt % 64 == 0
-                and n_w_gt > 0 and _standard_patch_offsets(target_raw["patch_area"], off)):
+        if self.reference_config(n_w_gt, pred_unsup["opacity"].shape[0], target_raw.get("patch_area", 0), off, rays_grad):
             return self._fused(pred_w_gt, target_gt, pred_unsup, dict(kwargs, count_job=pred_raw.get("_count_job")))
         job = pred_raw.get("_count_job")
         if job is not None:  # render left its sample count to the fused node, not used in this configuration
@@ -552,11 +558,10 @@ class NeRFMTLoss(nn.Module):
                          self.w_sched(self.norm_D_C_centr_L1_w, step))
                 if fuse_normals:
                     terms, _normals, labels, cents, raw = normals_cluster_losses(
-                        pred_unsup["rays_o"], pred_unsup["rays_d"], pred_unsup["depth"], pred_unsup["x123_idx"], K=20,
-                        niter=20, seed=self.kmeans_seed, t_similar=1.0 - self.norm_CAN_tres, w=w)
+                        pred_unsup["rays_o"], pred_unsup["rays_d"], pred_unsup["depth"], pred_unsup["x123_idx"],
+                        seed=self.kmeans_seed, t_similar=1.0 - self.norm_CAN_tres, w=w)
                 else:
-                    terms, labels, cents, raw = cluster_losses(pred_unsup["norm_depth"], K=20, niter=20,
-                                                               seed=self.kmeans_seed,
+                    terms, labels, cents, raw = cluster_losses(pred_unsup["norm_depth"], seed=self.kmeans_seed,
                                                                t_similar=1.0 - self.norm_CAN_tres, w=w)
                 loss_d["norm_D_C_ort_dot"] = terms[0]
                 loss_d["norm_D_C_centr_dot"] = terms[1]

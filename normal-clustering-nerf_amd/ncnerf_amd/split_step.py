@@ -36,13 +36,12 @@ import torch
 
 from . import _lib, vren
 from ._lib import call
-from .losses import N_OUT, _cluster_workspace, _standard_patch_offsets, kmeans_plan
+from .losses import K_CLUSTERS, K_ITERS, _STD_OFFSETS, cluster_launch
 from .ngp_mt import N_W
 from .rendering import march_train_fused
 
 SPLIT_BLOCKS = 240  # MLP-backward workgroups of each split pass at most: 256 CUs - the clustering's 16
-K_CLUSTERS, K_ITERS = 20, 20  # NeRFMTLoss._fused (losses.py:86-89: faiss.Kmeans(3, 20, niter=20))
-KM_BLOCKS = 16  # the clustering kernel's co-resident workgroups (csrc/loss.hip KM_BLOCKS)
+KM_BLOCKS = 16  # the clustering kernel's co-resident workgroups (csrc/cluster_ws.h KM_BLOCKS)
 
 
 def split_rgb_blocks(cus, per_cu, cap=SPLIT_BLOCKS):
@@ -64,18 +63,13 @@ def device_rgb_blocks():
 
 
 def split_eligible(trainer, batch):
-    """True when the step is the reference configuration the fused loss node serves (the condition
-    of NeRFMTLoss.forward's fused branch) on the static-shape white-background render."""
+    """True when the step is the reference configuration the fused loss node serves
+    (NeRFMTLoss.reference_config) on the static-shape white-background render."""
     L, m, kw = trainer.loss, trainer.model, trainer.render_kwargs
     R = batch["rays_o"].shape[0]
-    clustering = L.norm_D_C_ort_dot_w > 0 or L.norm_D_C_centr_dot_w > 0 or L.norm_D_C_centr_L1_w > 0
     off = {k: batch.get(k + "_offsets_local") for k in ("x1", "x2", "x3")}
-    return (clustering and L.pred_norm_depth and not L.random_tr_poses and L.opacity_w > 0 and L.distortion_w == 0
-            and L.ray_sampling_strategy in ("all_images_triang_patch", "same_image_triang_patch")
-            and L.depth_w == 0 and L.norm_DEpth_L1_w == 0 and L.norm_DEpth_dot_w == 0 and L.reg_depth_w == 0
-            and R > 0 and R % 64 == 0 and R <= 16384 and batch["rgb"].shape[0] == R
-            and not batch["rays_o"].requires_grad and not batch["rays_d"].requires_grad  # (pose refinement: autograd)
-            and all(v is not None for v in off.values()) and _standard_patch_offsets(batch.get("patch_area", 0), off)
+    rays_grad = batch["rays_o"].requires_grad or batch["rays_d"].requires_grad  # (pose refinement: autograd)
+    return (L.reference_config(batch["rgb"].shape[0], R, batch.get("patch_area", 0), off, rays_grad) and R <= 16384
             and not m.pred_norm and not m.pred_sem and getattr(m, "_aabb", None) is not None
             and kw.get("exp_step_factor", 0.0) == 0 and kw.get("anneal_strategy", "none") == "none"
             and not kw.get("random_bg", False)
@@ -97,22 +91,12 @@ class SplitStep:
         and RCCL's channels run beside the deferred coarse-level scatter, which leaves them 32 CUs,
         distributed.DP_SCATTER_BLOCKS.)"""
         self.tr = trainer
-        self._tri = None
         self.rgb_blocks = device_rgb_blocks() if rgb_blocks is None else int(rgb_blocks)
         if self.rgb_blocks < 1:
             raise _lib.NcnError("SplitStep: the device cannot hold the clustering's workgroups beside an rgb pass")
         cap = ctypes.c_int(0)
         call("ncn_cluster_coresidency", K_CLUSTERS, self.rgb_blocks, ctypes.byref(cap))
         self.cluster_capacity = cap.value
-
-    def _triangles(self, R, dev):
-        # the 8x8 patch triangles of losses.py:307-313 (x1/x2/x3 = the standard patch offsets)
-        if self._tri is None or self._tri[0] != R or self._tri[1] != dev:
-            pix = torch.arange(R, device=dev).view(-1, 64)
-            from .losses import _STD_OFFSETS
-            tri = tuple(pix[:, torch.as_tensor(o, device=dev)].reshape(-1).contiguous() for o in _STD_OFFSETS)
-            self._tri = (R, dev, tri)
-        return self._tri[2]
 
     def run(self, batch, step_dev, premarched=None):
         tr, m, L = self.tr, self.tr.model, self.tr.loss
@@ -134,7 +118,8 @@ class SplitStep:
         total_s, opacity, depth, rend, ws, rgb = vren.composite_train_multi_fw(sigmas, rgbs, deltas, ts, rays_a,
                                                                               T_thr, bg=1.0)
         # ---- NeRFMTLoss forward (_NeRFLossFused.forward) ----
-        x1, x2, x3 = self._triangles(R, dev)
+        tri = L.patch_triang_idx(R, 64, dict(zip(("x1", "x2", "x3"), _STD_OFFSETS)), dev)  # (the standard 8x8 patches)
+        x1, x2, x3 = tri["x1"], tri["x2"], tri["x3"]
         T = x1.shape[0]
         photo = torch.empty(4, dtype=torch.float32, device=dev)
         normals = torch.empty(T, 3, dtype=torch.float32, device=dev)
@@ -144,12 +129,6 @@ class SplitStep:
         # (the normals use results["rays_o"] = rays_d, rendering.py:227 quirk q1)
         call("ncn_photo_normals_count_fwd", rgb, rgb_gt, opacity, R, L.opacity_w, photo, rays_d, rays_d, depth, x1, x2,
              x3, T, normals, total_s, R, n_dev if acc is not None else None, cnt, acc)
-        out = torch.empty(N_OUT, dtype=torch.float32, device=dev)
-        labels = torch.empty(T, dtype=torch.int32, device=dev)
-        cents = torch.empty(K_CLUSTERS, 3, dtype=torch.float32, device=dev)
-        dn = torch.empty(3, T, 3, dtype=torch.float32, device=dev)
-        cws = _cluster_workspace(dev, K_CLUSTERS)
-        plan = kmeans_plan(dev, T, K_CLUSTERS, L.kmeans_seed)
         w = (L.norm_D_C_ort_dot_w, L.norm_D_C_centr_dot_w, L.norm_D_C_centr_L1_w)
         one = tr._unit(dev)
         lib = _lib.lib()
@@ -172,8 +151,8 @@ class SplitStep:
         cur = torch.cuda.current_stream(dev)
         side = tr._side_stream()
         side.wait_stream(cur)
-        call("ncn_cluster_loss", normals, T, K_CLUSTERS, K_ITERS, plan, 1.0 - L.norm_CAN_tres, w[0], w[1], w[2], None,
-             step_dev, float(L.can_sched_start), float(L._grow), photo, out, labels, cents, dn, cws)
+        out, labels, cents, dn = cluster_launch(normals, K_CLUSTERS, K_ITERS, L.kmeans_seed, 1.0 - L.norm_CAN_tres, w,
+                                                None, step_dev, (float(L.can_sched_start), float(L._grow)), photo)
         with torch.cuda.stream(side):
             # ---- photometric backward: loss -> composite -> field MLP (rgb part) ----
             call("ncn_nerf_loss_bwd", rgb, rgb_gt, opacity, R, L.opacity_w, photo, rays_d, rays_d, depth, None, one,
