@@ -17,7 +17,7 @@ namespace ncn {
 
 // ---- sampler ---------------------------------------------------------------------------------
 // splitmix64 output of the counter k under `seed`: the state seed + k * golden gamma through the
-// finaliser (the mixer of the marcher's jitter, vren.hip: march_uniform, restated here).
+// finaliser (the mixer of the marcher's jitter, vren_march_wave.h: march_uniform, restated here).
 __device__ __forceinline__ uint64_t splitmix64_at(uint64_t seed, uint64_t k) {
     uint64_t z = seed + 0x9E3779B97F4A7C15ull * k;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;

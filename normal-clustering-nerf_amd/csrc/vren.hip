@@ -6,1736 +6,65 @@
 // nvcc build contracts (default --fmad=true) are written as explicit fmaf(), identically in the
 // CPU oracle (oracle/vren_ref.c).  Division is IEEE (hipcc default correctly-rounded f32 div).
 // This makes sample positions, voxel indices and sample counts bit-identical to the oracle.
+//
+// This file holds the launchers and the C ABI.  The device code, by stage:
+//   vren_march.h         morton, mip, MarchConst, probe, skip; the serial walks (train and test)
+//   vren_march_wave.h    the wave-parallel walk at constant dt; the fused marcher's walk launch
+//   vren_march_pack.h    scan + pack (eager) and place (the fused marcher's second launch)
+//   vren_aabb.h          the slab test of one box, ray_aabb_intersect
+//   vren_composite.h     ray segments, CF_* and the long-ray dispatch; _fw.h / _bw.h: the compositors
+//   vren_test_loop.h     the test compositor, compaction, the device-driven test loop
+//   vren_util.h          morton / packbits kernels, count_samples, segment_csr
 #pragma clang fp contract(off)
 
 #include "common.h"
 #include "../../include/ncnerf.h"
-
-#define SQRT3 1.73205080757f
-
-namespace ncn {
-
-__device__ __forceinline__ float clampf_(float f, float a, float b) { return fmaxf(a, fminf(f, b)); }
-__device__ __forceinline__ float signf_(float x) { return copysignf(1.0f, x); }
-
-__device__ __forceinline__ uint32_t expand_bits(uint32_t v) {
-    v = (v * 0x00010001u) & 0xFF0000FFu;
-    v = (v * 0x00000101u) & 0x0F00F00Fu;
-    v = (v * 0x00000011u) & 0xC30C30C3u;
-    v = (v * 0x00000005u) & 0x49249249u;
-    return v;
-}
-// raymarching.cu:44-50
-__device__ __forceinline__ uint32_t morton3D(uint32_t x, uint32_t y, uint32_t z) {
-    return expand_bits(x) | (expand_bits(y) << 1) | (expand_bits(z) << 2);
-}
-// raymarching.cu:52-60
-__device__ __forceinline__ uint32_t morton3D_invert(uint32_t x) {
-    x = x & 0x49249249u;
-    x = (x | (x >> 2)) & 0xc30c30c3u;
-    x = (x | (x >> 4)) & 0x0f00f00fu;
-    x = (x | (x >> 8)) & 0xff0000ffu;
-    x = (x | (x >> 16)) & 0x0000ffffu;
-    return x;
-}
-
-// raymarching.cu:19-32
-__device__ __forceinline__ int mip_from_pos(float x, float y, float z, int cascades) {
-    const float mx = fmaxf(fabsf(x), fmaxf(fabsf(y), fabsf(z)));
-    int e;
-    frexpf(mx, &e);
-    return min(cascades - 1, max(0, e + 1));
-}
-__device__ __forceinline__ int mip_from_dt(float dt, int grid_size, int cascades) {
-    int e;
-    frexpf(dt * (float)grid_size, &e);
-    return min(cascades - 1, max(0, e));
-}
-
-// Marcher constants.  calc_dt (raymarching.cu:11-13) = clamp(t*esf, SQRT3/max_samples, SQRT3*2*scale/G)
-struct MarchConst {
-    float esf, dt_min, dt_max, scale, gsi;
-    int cascades, G, max_samples;
-    uint32_t G3;
-};
-__device__ __forceinline__ MarchConst make_march_const(int cascades, float scale, float esf, int G, int max_samples,
-                                                       float dt_scale) {
-    MarchConst m;
-    m.esf = esf;
-    m.dt_min = SQRT3 / (float)max_samples;
-    m.dt_max = SQRT3 * 2 * dt_scale / (float)G;
-    m.scale = scale;
-    m.gsi = 1.0f / (float)G;
-    m.cascades = cascades;
-    m.G = G;
-    m.max_samples = max_samples;
-    m.G3 = (uint32_t)G * G * G;
-    return m;
-}
-__device__ __forceinline__ float calc_dt(const MarchConst& m, float t) { return clampf_(t * m.esf, m.dt_min, m.dt_max); }
-
-// One occupancy probe at t (raymarching.cu:205-220).  Returns the voxel (nx,ny,nz), mip bound and
-// the bitfield index; `cache_bi/cache_b` memoise the last bitfield byte (same byte => same bits).
-template <bool ONE_CASCADE>
-__device__ __forceinline__ bool probe(const MarchConst& m, const uint8_t* __restrict__ bitfield, float x, float y,
-                                      float z, float dt, int& nx, int& ny, int& nz, float& mip_bound,
-                                      uint32_t& cache_bi, uint32_t& cache_b) {
-    int mip;
-    if (ONE_CASCADE) {
-        mip = 0;  // min(cascades-1, ...) == 0 for both mip_from_pos and mip_from_dt
-    } else {
-        mip = max(mip_from_pos(x, y, z, m.cascades), mip_from_dt(dt, m.G, m.cascades));
-    }
-    mip_bound = fminf(scalbnf(1.0f, mip - 1), m.scale);
-    const float mip_bound_inv = 1.0f / mip_bound;
-    nx = (int)clampf_(0.5f * fmaf(x, mip_bound_inv, 1.0f) * (float)m.G, 0.0f, m.G - 1.0f);
-    ny = (int)clampf_(0.5f * fmaf(y, mip_bound_inv, 1.0f) * (float)m.G, 0.0f, m.G - 1.0f);
-    nz = (int)clampf_(0.5f * fmaf(z, mip_bound_inv, 1.0f) * (float)m.G, 0.0f, m.G - 1.0f);
-    const uint32_t idx = (uint32_t)mip * m.G3 + morton3D((uint32_t)nx, (uint32_t)ny, (uint32_t)nz);
-    const uint32_t bi = idx >> 3;
-    if (bi != cache_bi) {
-        cache_b = bitfield[bi];
-        cache_bi = bi;
-    }
-    return (cache_b >> (idx & 7)) & 1u;
-}
-
-// Empty-voxel skip (raymarching.cu:224-233).
-__device__ __forceinline__ float skip_voxel(const MarchConst& m, float t, float x, float y, float z, float dx,
-                                            float dy, float dz, float dxi, float dyi, float dzi, int nx, int ny,
-                                            int nz, float mip_bound) {
-    const float tx = fmaf(fmaf(0.5f, signf_(dx), (float)nx + 0.5f) * m.gsi * 2 - 1, mip_bound, -x) * dxi;
-    const float ty = fmaf(fmaf(0.5f, signf_(dy), (float)ny + 0.5f) * m.gsi * 2 - 1, mip_bound, -y) * dyi;
-    const float tz = fmaf(fmaf(0.5f, signf_(dz), (float)nz + 0.5f) * m.gsi * 2 - 1, mip_bound, -z) * dzi;
-    const float t_target = t + fmaxf(0.0f, fminf(tx, fminf(ty, tz)));
-    do {
-        t += calc_dt(m, t);
-    } while (t < t_target);
-    return t;
-}
-
-// ---------------------------------------------------------------------------------------------
-// raymarching_train pass 1: one lane per ray walks it once (raymarching.cu:184-234) and writes the
-// samples into its slab row.  64-lane workgroups spread the (latency-bound) walks over the CUs.
-template <bool ONE_CASCADE>
-__global__ __launch_bounds__(64) void march_train_walk_kernel(
-    const float* __restrict__ rays_o, const float* __restrict__ rays_d, const float* __restrict__ hits_t,
-    const float* __restrict__ noise, int64_t R, const uint8_t* __restrict__ bitfield, int cascades, float scale,
-    float esf, int G, int max_samples, int32_t* __restrict__ counts, float* __restrict__ slab_xyz,
-    float* __restrict__ slab_t, float* __restrict__ slab_dt) {
-    const int64_t r = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (r >= R) return;
-    const MarchConst m = make_march_const(cascades, scale, esf, G, max_samples, scale);
-    const float ox = rays_o[3 * r], oy = rays_o[3 * r + 1], oz = rays_o[3 * r + 2];
-    const float dx = rays_d[3 * r], dy = rays_d[3 * r + 1], dz = rays_d[3 * r + 2];
-    const float dxi = 1.0f / dx, dyi = 1.0f / dy, dzi = 1.0f / dz;
-    float t1 = hits_t[2 * r];
-    const float t2 = hits_t[2 * r + 1];
-    if (t1 >= 0) {  // :195-198
-        const float dt = calc_dt(m, t1);
-        t1 = fmaf(dt, noise[r], t1);
-    }
-    float* sx = slab_xyz + r * (int64_t)max_samples * 3;
-    float* st = slab_t + r * (int64_t)max_samples;
-    float* sd = slab_dt + r * (int64_t)max_samples;
-    uint32_t cache_bi = 0xFFFFFFFFu, cache_b = 0;
-    float t = t1;
-    int n = 0;
-    while (0 <= t && t < t2 && n < max_samples) {  // :204
-        const float x = fmaf(t, dx, ox), y = fmaf(t, dy, oy), z = fmaf(t, dz, oz);
-        const float dt = calc_dt(m, t);
-        int nx, ny, nz;
-        float mip_bound;
-        if (probe<ONE_CASCADE>(m, bitfield, x, y, z, dt, nx, ny, nz, mip_bound, cache_bi, cache_b)) {
-            sx[3 * n] = x;
-            sx[3 * n + 1] = y;
-            sx[3 * n + 2] = z;
-            st[n] = t;
-            sd[n] = dt;
-            t += dt;
-            n++;
-        } else {
-            t = skip_voxel(m, t, x, y, z, dx, dy, dz, dxi, dyi, dzi, nx, ny, nz, mip_bound);
-        }
-    }
-    counts[r] = n;
-}
-
-// ---------------------------------------------------------------------------------------------
-// raymarching_train pass 1, wave-parallel form (exp_step_factor == 0, i.e. constant dt; the
-// reference's configs at scale 0.5).  Both branches of the reference walk advance t along the same
-// chain c_{k+1} = fl(c_k + dt): an occupied probe emits and does `t += dt`, an empty one does
-// `do t += dt; while (t < t_target)` (raymarching.cu:221-233).  So the walk visits a subsequence of
-// that chain: after an occupied position k comes k+1, after an empty one the first j > k with
-// c_j >= t_target(k).  One wave takes one ray, 64*P chain positions per iteration (lane l holds
-// positions l + 64 j): the chain values come in closed form (march_chain), every position is
-// probed at once (one bitfield gather per lane instead of one serial walk step), and a short
-// scalar loop over ballot masks resolves which positions the walk visits.  Emitted samples are
-// compacted (mbcnt) into the slab row.  Bit-identical to the serial walk: same fmaf positions,
-// same probe, same target expression, same chain values.
-
-// Chain values in closed form.  Inside one binade [2^e, 2^(e+1)) with ulp u, c + dt rounds to
-// c + u*round(dt/u) when dt/u is not a tie, i.e. a constant step in the bit pattern; with a tie
-// (dt/u = m + 1/2, possible in at most one binade) round-to-even makes every result even, so the
-// step is constant from the second step on.  The two first steps are real float adds (r1, r) and
-// the rest of the binade is bits(v) + r1 + (k-1) r, valid while the exponent field is unchanged
-// (then the exact sum is below 2^(e+1), so the in-binade rounding applies); the step that leaves
-// the binade is again a real float add.  Fills c[j] = c_{lane + 64 j} for the window starting at
-// cb (index 0) and returns c_{64P}.  A chain that stops advancing (dt < u/2: the reference would
-// spin forever) is frozen and the caller's window cap ends the ray.
-template <int P>
-__device__ __forceinline__ float march_chain(float cb, float dt, int lane, float (&c)[P]) {
-    constexpr int L = 64 * P;
-#pragma unroll
-    for (int j = 0; j < P; j++) c[j] = cb;
-    int j0 = 0;
-    float v = cb;
-    for (;;) {
-        const uint32_t bv = __float_as_uint(v);
-        const float v1 = v + dt;
-        const uint32_t b1 = __float_as_uint(v1);
-        uint32_t r1 = b1 - bv, r = 0;
-        int K;
-        float vn;
-        if ((bv >> 23) != (b1 >> 23) || bv == 0u) {
-            K = 0;
-            vn = v1;
-        } else {
-            const float v2 = v1 + dt;
-            const uint32_t b2 = __float_as_uint(v2);
-            if ((b2 >> 23) != (b1 >> 23)) {
-                K = 1;
-                vn = v2;
-            } else {
-                r = b2 - b1;
-                if (r == 0u) {  // frozen chain (reference: endless loop)
-#pragma unroll
-                    for (int j = 0; j < P; j++)
-                        if (lane + 64 * j > j0) c[j] = v;
-                    return v;
-                }
-                const uint32_t room = (bv | 0x7FFFFFu) - bv - r1;  // bits left in the binade after step 1
-                // steps in the binade: room / r + 1 (the division only when the binade ends in the window)
-                K = (uint64_t)room >= (uint64_t)(L - 1) * r ? L : (int)(room / r + 1u);
-                vn = __uint_as_float(bv + r1 + (uint32_t)(K - 1) * r) + dt;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < P; j++) {
-            const int i = lane + 64 * j;
-            if (i > j0 && i <= j0 + K) c[j] = __uint_as_float(bv + r1 + (uint32_t)(i - j0 - 1) * r);
-        }
-        if (j0 + K >= L) return __uint_as_float(bv + r1 + (uint32_t)(L - j0 - 1) * r);
-        const int J = j0 + K + 1;
-        if (J == L) return vn;
-#pragma unroll
-        for (int j = 0; j < P; j++)
-            if (lane + 64 * j == J) c[j] = vn;
-        j0 = J;
-        v = vn;
-    }
-}
-
-// c[] as seen from lane `idx` (idx in [0, 63])
-__device__ __forceinline__ float lane_f(float v, int idx) { return __int_as_float(__builtin_amdgcn_ds_bpermute(idx << 2, __float_as_int(v))); }
-__device__ __forceinline__ int lane_i(int v, int idx) { return __builtin_amdgcn_ds_bpermute(idx << 2, v); }
-
-// First lane j > lane whose chain value reaches T (64 if none): the position an empty probe's skip
-// lands on (do t += dt while t < T).  The chain steps are dt up to rounding (< ulp/2 each), so
-// lane + ceil((T - c)/dt) is within one of the answer; one check either side fixes it, and a wave
-// whose estimate still fails (only for steps far off dt) falls back to a binary search.
-__device__ __forceinline__ int march_skip_lane(float c, float T, float dt, int lane) {
-    const float q = ceilf((T - c) / dt);
-    int j = lane + (int)fminf(fmaxf(q, 1.0f), 65.0f);
-    if (j > 64) j = 64;
-    const float cm = lane_f(c, min(j - 1, 63));  // c at j - 1 (>= lane)
-    const float cj = lane_f(c, min(j, 63));
-    if (j - 1 > lane && cm >= T) j -= 1;
-    else if (j < 64 && cj < T) j += 1;
-    const float cm2 = lane_f(c, min(j - 1, 63));
-    const float cj2 = lane_f(c, min(j, 63));
-    const bool ok = (j - 1 == lane || cm2 < T) && (j == 64 || cj2 >= T);
-    if (__ballot(!ok)) {  // binary search: last position p >= lane with c_p < T, answer p + 1
-        int p = lane;
-#pragma unroll
-        for (int st = 32; st >= 1; st >>= 1) {
-            const int qn = p + st;
-            const float cq = lane_f(c, min(qn, 63));
-            if (qn <= 63 && cq < T) p = qn;
-        }
-        j = p + 1;
-    }
-    return j;
-}
-
-// Positions the walk visits in this sub-window, starting at lane s (uniform), given every lane's
-// successor nxt (> lane; 64 = beyond): binary lifting over nxt (jump tables of 1, 2, 4 .. 32 steps),
-// then every lane walks the largest jumps from s that do not pass it and checks where it lands.
-__device__ __forceinline__ uint64_t march_visited(int nxt, int s, int lane) {
-    int J[6];
-    J[0] = nxt;
-#pragma unroll
-    for (int i = 1; i < 6; i++) {
-        const int v = lane_i(J[i - 1], min(J[i - 1], 63));
-        J[i] = J[i - 1] >= 64 ? 64 : v;
-    }
-    int cur = s;
-#pragma unroll
-    for (int i = 5; i >= 0; i--) {
-        const int v = lane_i(J[i], min(cur, 63));
-        const int cand = cur >= 64 ? 64 : v;
-        if (cand <= lane) cur = cand;
-    }
-    return __ballot(cur == lane && lane >= s);
-}
-
-// The wave-parallel walk of one ray (raymarching.cu:195-279 with constant dt): samples to the
-// ray's slab row (sx/st/sd), returns their count (wave-uniform).
-template <bool ONE_CASCADE, int P>
-__device__ __forceinline__ int march_walk_wave(const MarchConst& m, const uint8_t* __restrict__ bitfield, float ox,
-                                               float oy, float oz, float dx, float dy, float dz, float t1, float t2,
-                                               float noise_r, float dt, int lane, float* __restrict__ sx,
-                                               float* __restrict__ st, float* __restrict__ sd) {
-    const float dxi = 1.0f / dx, dyi = 1.0f / dy, dzi = 1.0f / dz;
-    int n = 0;
-    if (t1 >= 0) {  // :195-198; a miss (t1 = -1) never enters the loop (:204)
-        t1 = fmaf(dt, noise_r, t1);
-        float cb = t1;
-        bool pend = false, done = false;
-        float ptgt = 0.f;
-        int s = 0;  // next visited lane of the current sub-window (when !pend)
-        for (int it = 0; it < (1 << 16) && !done; it++) {
-            float c[P];
-            const float cnext = march_chain<P>(cb, dt, lane, c);
-            float X[P], Y[P], Z[P], tgt[P];
-            bool occ[P];
-#pragma unroll
-            for (int j = 0; j < P; j++) {
-                X[j] = fmaf(c[j], dx, ox);
-                Y[j] = fmaf(c[j], dy, oy);
-                Z[j] = fmaf(c[j], dz, oz);
-                int nx, ny, nz;
-                float mip_bound;
-                uint32_t cbi = 0xFFFFFFFFu, cbv = 0;
-                occ[j] = probe<ONE_CASCADE>(m, bitfield, X[j], Y[j], Z[j], dt, nx, ny, nz, mip_bound, cbi, cbv);
-                // skip_voxel's target (raymarching.cu:224-229) for an empty probe at this position
-                const float tx =
-                    fmaf(fmaf(0.5f, signf_(dx), (float)nx + 0.5f) * m.gsi * 2 - 1, mip_bound, -X[j]) * dxi;
-                const float ty =
-                    fmaf(fmaf(0.5f, signf_(dy), (float)ny + 0.5f) * m.gsi * 2 - 1, mip_bound, -Y[j]) * dyi;
-                const float tz =
-                    fmaf(fmaf(0.5f, signf_(dz), (float)nz + 0.5f) * m.gsi * 2 - 1, mip_bound, -Z[j]) * dzi;
-                tgt[j] = c[j] + fmaxf(0.0f, fminf(tx, fminf(ty, tz)));
-            }
-#pragma unroll
-            for (int j = 0; j < P; j++) {
-                if (done) break;
-                const uint64_t lt_m = __ballot(c[j] < t2);  // loop condition t < t2 (:204)
-                const uint64_t occ_m = __ballot(occ[j]);
-                if (pend) {
-                    const uint64_t mm = __ballot(c[j] >= ptgt);
-                    if (!mm) continue;  // the skip runs past this sub-window
-                    s = __builtin_ctzll(mm);
-                    pend = false;
-                }
-                // successor of every position if the walk visits it (64 = beyond this sub-window)
-                // (march_skip_lane reads other lanes: evaluated by the whole wave, then selected)
-                const int skip = march_skip_lane(c[j], tgt[j], dt, lane);
-                const int nxt = !(c[j] < t2) ? 64 : (occ[j] ? lane + 1 : skip);  // 64: the walk ends here
-                const uint64_t vis = march_visited(nxt, s, lane);
-                const uint64_t term = vis & ~lt_m;
-                uint64_t emit = vis & occ_m & lt_m;
-                const int room = m.max_samples - n;
-                if (__popcll(emit) >= room) {  // the room-th sample ends the walk (:204 n < m.max_samples)
-                    uint64_t e2 = emit;
-                    for (int q = 1; q < room; q++) e2 &= e2 - 1;
-                    const int last = __builtin_ctzll(e2);
-                    emit &= (last == 63) ? ~0ull : ((2ull << last) - 1);
-                    done = true;
-                }
-                if (term) {
-                    emit &= (1ull << __builtin_ctzll(term)) - 1;
-                    done = true;
-                }
-                if (emit) {
-                    if ((emit >> lane) & 1) {
-                        const int k = n + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(emit >> 32),
-                                                                       __builtin_amdgcn_mbcnt_lo((uint32_t)emit, 0));
-                        sx[3 * k] = X[j];
-                        sx[3 * k + 1] = Y[j];
-                        sx[3 * k + 2] = Z[j];
-                        st[k] = c[j];
-                        sd[k] = dt;
-                    }
-                    n += __popcll(emit);
-                }
-                if (!done) {  // carry: after the last visited position
-                    const int lastv = 63 - __builtin_clzll(vis);
-                    if ((occ_m >> lastv) & 1) {
-                        s = 0;  // emitted at lane lastv (== 63): the next position is lane 0 of the next sub-window
-                    } else {
-                        pend = true;  // an empty position whose skip target lies past this sub-window
-                        ptgt = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tgt[j]), lastv));
-                    }
-                }
-            }
-            cb = cnext;
-        }
-    }
-    return n;
-}
-
-template <bool ONE_CASCADE, int P>
-__global__ __launch_bounds__(256) void march_train_wave_kernel(
-    const float* __restrict__ rays_o, const float* __restrict__ rays_d, const float* __restrict__ hits_t,
-    const float* __restrict__ noise, int64_t R, const uint8_t* __restrict__ bitfield, int cascades, float scale,
-    int G, int max_samples, int32_t* __restrict__ counts, float* __restrict__ slab_xyz,
-    float* __restrict__ slab_t, float* __restrict__ slab_dt) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
-    if (r >= R) return;
-    const MarchConst m = make_march_const(cascades, scale, 0.0f, G, max_samples, scale);
-    const float t1 = hits_t[2 * r];
-    const int n = march_walk_wave<ONE_CASCADE, P>(
-        m, bitfield, rays_o[3 * r], rays_o[3 * r + 1], rays_o[3 * r + 2], rays_d[3 * r], rays_d[3 * r + 1],
-        rays_d[3 * r + 2], t1, hits_t[2 * r + 1], t1 >= 0 ? noise[r] : 0.f, calc_dt(m, 0.0f), lane,
-        slab_xyz + r * (int64_t)max_samples * 3, slab_t + r * (int64_t)max_samples, slab_dt + r * (int64_t)max_samples);
-    if (lane == 0) counts[r] = n;
-}
-
-// raymarching_train pass 2: exclusive scan of the counts in ray order (one workgroup; replaces the
-// atomicAdd start offsets of raymarching.cu:237-241) -> rays_a, counter = {S, R}.
-__global__ __launch_bounds__(1024) void march_train_scan_kernel(const int32_t* __restrict__ counts, int64_t R,
-                                                                int64_t* __restrict__ rays_a,
-                                                                int32_t* __restrict__ counter) {
-    __shared__ int wave_tot[16];
-    __shared__ int carry_s;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    if (tid == 0) carry_s = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < R; base += 4096) {
-        const int64_t i0 = base + (int64_t)tid * 4;
-        int c[4];
-        int local = 0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            c[j] = (i0 + j < R) ? counts[i0 + j] : 0;
-            local += c[j];
-        }
-        int incl = local;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            int o = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += o;
-        }
-        if (lane == 63) wave_tot[wid] = incl;
-        __syncthreads();
-        int wave_off = 0, block_tot = 0;
-        for (int w = 0; w < 16; w++) {
-            if (w < wid) wave_off += wave_tot[w];
-            block_tot += wave_tot[w];
-        }
-        const int carry = carry_s;
-        int run = carry + wave_off + incl - local;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int64_t i = i0 + j;
-            if (i < R) {
-                rays_a[3 * i] = i;
-                rays_a[3 * i + 1] = run;
-                rays_a[3 * i + 2] = c[j];
-            }
-            run += c[j];
-        }
-        __syncthreads();
-        if (tid == 0) carry_s = carry + block_tot;
-        __syncthreads();
-    }
-    if (tid == 0) {
-        counter[0] = carry_s;
-        counter[1] = (int32_t)R;
-    }
-}
-
-// raymarching_train pass 3: one wave per ray copies its slab row to the packed outputs
-// (coalesced 4-byte lanes) and broadcasts the ray direction into dirs (raymarching.cu:263-268).
-__global__ __launch_bounds__(256) void march_train_pack_kernel(
-    const float* __restrict__ rays_d, const int64_t* __restrict__ rays_a, int64_t R, int max_samples,
-    const float* __restrict__ slab_xyz, const float* __restrict__ slab_t, const float* __restrict__ slab_dt,
-    float* __restrict__ xyzs, float* __restrict__ dirs, float* __restrict__ deltas, float* __restrict__ ts) {
-    const int lane = threadIdx.x & 63;
-    // wave-uniform ray index (readfirstlane: the per-ray loads below become scalar s_loads)
-    const int64_t n = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
-    if (n >= R) return;
-    const int64_t ray = rays_a[3 * n], start = rays_a[3 * n + 1];
-    const int cnt = (int)rays_a[3 * n + 2];
-    const float d3[3] = {rays_d[3 * ray], rays_d[3 * ray + 1], rays_d[3 * ray + 2]};
-    const float* sx = slab_xyz + ray * (int64_t)max_samples * 3;
-    const float* st = slab_t + ray * (int64_t)max_samples;
-    const float* sd = slab_dt + ray * (int64_t)max_samples;
-    for (int k = lane; k < 3 * cnt; k += 64) {
-        xyzs[3 * start + k] = sx[k];
-        dirs[3 * start + k] = d3[k % 3];
-    }
-    for (int k = lane; k < cnt; k += 64) {
-        ts[start + k] = st[k];
-        deltas[start + k] = sd[k];
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// raymarching_train for the training step in TWO launches (constant dt), replacing ray_aabb +
-// rand + walk + scan + pack:
-//  1. march_train_walk2: per ray (one wave) the single-AABB intersection with render()'s near
-//     clamp (intersection.cu:5-56 at max_hits 1, rendering.py:28; bit-identical to
-//     ray_aabb_kernel<1>), the jitter (custom_functions.py:83: torch.rand_like; here `noise` or, when
-//     NULL, a counter-based uniform of (seed, *rng_ctr, ray)), the walk into the ray's slab row;
-//     counts per ray and the sum of each workgroup's 4 rays;
-//  2. march_train_place: every workgroup sums the sums of the workgroups before it (all loads in
-//     one round trip, no inter-workgroup waiting), places its 4 rays (rays_a) and copies their slab
-//     rows into the packed outputs; the last workgroup writes counter = {S, R}.
-// (A single-pass decoupled look-back version was slower: the look-back of late workgroups walks
-// back through many not-yet-prefixed predecessors, one memory round trip per 64 of them.)
-__device__ __forceinline__ float march_uniform(uint64_t seed, uint64_t ctr, uint32_t r) {
-    uint64_t z = seed + 0x9E3779B97F4A7C15ull * (ctr * 0x100000001B3ull + r + 1u);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);
-}
-
-constexpr int PLACE_MAX_WG = 256 * 16;  // workgroup sums one place workgroup can add in one round trip
-// rays_a ROW order of the training step: rays with more than PLACE_LONG samples (more than one
-// round of the compositors' row blocks) take the first rows, so the compositors dispatch their
-// waves first and their extra round trip overlaps the rest of the launch.  Sample segments stay in
-// ray order.  (The reference's rows and starts are both in atomicAdd order, raymarching.cu:237-241:
-// any row order is within its contract; consumers index outputs by rays_a[:, 0].)
-constexpr int PLACE_LONG = 256;
-
-template <bool ONE_CASCADE, int P>
-__global__ __launch_bounds__(256) void march_train_walk2_kernel(
-    const float* __restrict__ rays_o, const float* __restrict__ rays_d, int64_t R, float cx, float cy, float cz,
-    float hx, float hy, float hz, float near_distance, const float* __restrict__ noise, uint64_t seed,
-    const int64_t* __restrict__ rng_ctr, const uint8_t* __restrict__ bitfield, int cascades, float scale, int G,
-    int max_samples, float* __restrict__ slab_xyz, float* __restrict__ slab_t, float* __restrict__ slab_dt,
-    int32_t* __restrict__ counts, int32_t* __restrict__ wg_sum) {
-    __shared__ int cnt_s[4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t r0 = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + wv));
-    const bool live = r0 < R;
-    const int64_t r = live ? r0 : R - 1;
-    const MarchConst m = make_march_const(cascades, scale, 0.0f, G, max_samples, scale);
-    const float o[3] = {rays_o[3 * r], rays_o[3 * r + 1], rays_o[3 * r + 2]};
-    const float d[3] = {rays_d[3 * r], rays_d[3 * r + 1], rays_d[3 * r + 2]};
-    const float c3[3] = {cx, cy, cz}, h3[3] = {hx, hy, hz};
-    float a1[3], a2[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const float inv = 1.0f / d[k];
-        const float tmin = (c3[k] - h3[k] - o[k]) * inv;
-        const float tmax = (c3[k] + h3[k] - o[k]) * inv;
-        a1[k] = fminf(tmin, tmax);
-        a2[k] = fmaxf(tmin, tmax);
-    }
-    float t1 = fmaxf(fmaxf(a1[0], a1[1]), a1[2]);
-    float t2 = fminf(fminf(a2[0], a2[1]), a2[2]);
-    if (t1 > t2) { t1 = -1.0f; t2 = -1.0f; }
-    if (t2 > 0) t1 = fmaxf(t1, 0.0f);
-    else { t1 = -1.0f; t2 = -1.0f; }
-    if (t1 >= 0.0f && t1 < near_distance) t1 = near_distance;
-    float nz = 0.f;
-    if (t1 >= 0) nz = noise ? noise[r] : march_uniform(seed, rng_ctr ? (uint64_t)*rng_ctr : 0ull, (uint32_t)r);
-    int n = 0;
-    if (live)
-        n = march_walk_wave<ONE_CASCADE, P>(m, bitfield, o[0], o[1], o[2], d[0], d[1], d[2], t1, t2, nz,
-                                            calc_dt(m, 0.0f), lane, slab_xyz + r * (int64_t)max_samples * 3,
-                                            slab_t + r * (int64_t)max_samples, slab_dt + r * (int64_t)max_samples);
-    if (lane == 0) {
-        cnt_s[wv] = n;
-        if (live) counts[r] = n;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {  // sample sum | number of long rays << 26 (rays placed first by march_train_place)
-        int nl = 0;
-#pragma unroll
-        for (int w = 0; w < 4; w++) nl += cnt_s[w] > PLACE_LONG;
-        wg_sum[blockIdx.x] = (cnt_s[0] + cnt_s[1] + cnt_s[2] + cnt_s[3]) | (nl << 26);
-    }
-}
-
-__global__ __launch_bounds__(256) void march_train_place_kernel(
-    const float* __restrict__ rays_d, int64_t R, int max_samples, const int32_t* __restrict__ counts,
-    const int32_t* __restrict__ wg_sum, const float* __restrict__ slab_xyz, const float* __restrict__ slab_t,
-    const float* __restrict__ slab_dt, int64_t* __restrict__ rays_a, float* __restrict__ xyzs,
-    float* __restrict__ dirs, float* __restrict__ deltas, float* __restrict__ ts, int32_t* __restrict__ counter) {
-    __shared__ int red[4], redl[4], redt[4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int b = blockIdx.x;
-    // exclusive prefix over the workgroup sums [0, b) and the total of long rays: 16 loads per
-    // thread (every workgroup's word), all in flight
-    int v[PLACE_MAX_WG / 256];
-#pragma unroll
-    for (int u = 0; u < PLACE_MAX_WG / 256; u++) {
-        const int i = u * 256 + threadIdx.x;
-        v[u] = i < (int)gridDim.x ? wg_sum[i] : 0;
-    }
-    const int64_t r0 = __builtin_amdgcn_readfirstlane((int)(b * 4 + wv));
-    const bool live = r0 < R;
-    const int64_t r = live ? r0 : R - 1;
-    const int n = live ? counts[r] : 0;
-    // the first 256 samples of the ray's slab row are fetched while the prefix is formed
-    const float d3[3] = {rays_d[3 * r], rays_d[3 * r + 1], rays_d[3 * r + 2]};
-    const float* sx = slab_xyz + r * (int64_t)max_samples * 3;
-    const float* st = slab_t + r * (int64_t)max_samples;
-    const float* sd = slab_dt + r * (int64_t)max_samples;
-    constexpr int PF = 4;  // rows of 64 prefetched (xyz: 3 floats per sample -> 3*PF loads)
-    float px[3 * PF], pt[PF], pd[PF];
-#pragma unroll
-    for (int q = 0; q < 3 * PF; q++) px[q] = q * 64 + lane < 3 * n ? sx[q * 64 + lane] : 0.f;
-#pragma unroll
-    for (int q = 0; q < PF; q++) {
-        pt[q] = q * 64 + lane < n ? st[q * 64 + lane] : 0.f;
-        pd[q] = q * 64 + lane < n ? sd[q * 64 + lane] : 0.f;
-    }
-    int acc = 0, lpre = 0, ltot = 0;  // samples before this workgroup, long rays before it, in all
-#pragma unroll
-    for (int u = 0; u < PLACE_MAX_WG / 256; u++) {
-        const int i = u * 256 + threadIdx.x;
-        const int nl = (int)((unsigned)v[u] >> 26);
-        if (i < b) {
-            acc += v[u] & ((1 << 26) - 1);
-            lpre += nl;
-        }
-        ltot += nl;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        acc += __shfl_xor(acc, off, 64);
-        lpre += __shfl_xor(lpre, off, 64);
-        ltot += __shfl_xor(ltot, off, 64);
-    }
-    if (lane == 0) { red[wv] = acc; redl[wv] = lpre; redt[wv] = ltot; }
-    __syncthreads();
-    int start = red[0] + red[1] + red[2] + red[3];
-    const int long_before = redl[0] + redl[1] + redl[2] + redl[3];
-    const int long_total = redt[0] + redt[1] + redt[2] + redt[3];
-    __syncthreads();
-    if (lane == 0) red[wv] = n;
-    __syncthreads();
-    int lw = 0;  // long rays among the earlier waves of this workgroup
-    for (int w = 0; w < wv; w++) {
-        start += red[w];
-        lw += red[w] > PLACE_LONG;
-    }
-    const int64_t row = n > PLACE_LONG ? (int64_t)(long_before + lw)
-                                       : (int64_t)long_total + (4 * (int64_t)b - long_before) + (wv - lw);
-    if (b == (int)gridDim.x - 1 && threadIdx.x == 0) {
-        counter[0] = start + red[0] + red[1] + red[2] + red[3];  // (thread 0: start = the workgroup's prefix)
-        counter[1] = (int32_t)R;
-    }
-    if (!live) return;
-    if (lane == 0) {
-        rays_a[3 * row] = r;
-        rays_a[3 * row + 1] = start;
-        rays_a[3 * row + 2] = n;
-    }
-    float* ox = xyzs + 3 * (int64_t)start;
-    float* od = dirs + 3 * (int64_t)start;
-#pragma unroll
-    for (int q = 0; q < 3 * PF; q++) {
-        const int k = q * 64 + lane;
-        if (k < 3 * n) {
-            ox[k] = px[q];
-            od[k] = d3[k % 3];
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < PF; q++) {
-        const int k = q * 64 + lane;
-        if (k < n) {
-            ts[start + k] = pt[q];
-            deltas[start + k] = pd[q];
-        }
-    }
-    for (int k = 3 * PF * 64 + lane; k < 3 * n; k += 64) {
-        ox[k] = sx[k];
-        od[k] = d3[k % 3];
-    }
-    for (int k = PF * 64 + lane; k < n; k += 64) {
-        ts[start + k] = st[k];
-        deltas[start + k] = sd[k];
-    }
-}
-
-// raymarching_test (raymarching.cu:335-404): one lane per alive ray; writes all N_samples slots
-// (zeros past n_eff, as the torch::zeros outputs of :422-427).  Quirk q3: calc_dt receives
-// `cascades` as its scale (:370, :399).
-template <bool ONE_CASCADE>
-__global__ __launch_bounds__(64) void march_test_kernel(const float* __restrict__ rays_o,
-                                                        const float* __restrict__ rays_d, float* __restrict__ hits_t,
-                                                        const int64_t* __restrict__ alive, int64_t A,
-                                                        const uint8_t* __restrict__ bitfield, int cascades,
-                                                        float scale, float esf, int G, int max_samples, int NS,
-                                                        float* __restrict__ xyzs, float* __restrict__ dirs,
-                                                        float* __restrict__ deltas, float* __restrict__ ts,
-                                                        int32_t* __restrict__ n_eff, const int32_t* __restrict__ ctrl) {
-    if (ctrl) {  // (device-driven test loop) alive count and samples per ray of this iteration
-        A = ctrl[0];
-        NS = ctrl[1];
-    }
-    const int64_t n = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (n >= A) return;
-    const MarchConst m = make_march_const(cascades, scale, esf, G, max_samples, (float)cascades);
-    const int64_t r = alive[n];
-    const float ox = rays_o[3 * r], oy = rays_o[3 * r + 1], oz = rays_o[3 * r + 2];
-    const float dx = rays_d[3 * r], dy = rays_d[3 * r + 1], dz = rays_d[3 * r + 2];
-    const float dxi = 1.0f / dx, dyi = 1.0f / dy, dzi = 1.0f / dz;
-    float t = hits_t[2 * r];
-    const float t2 = hits_t[2 * r + 1];
-    float* X = xyzs + n * (int64_t)NS * 3;
-    float* D = dirs + n * (int64_t)NS * 3;
-    float* DT = deltas + n * (int64_t)NS;
-    float* TS = ts + n * (int64_t)NS;
-    uint32_t cache_bi = 0xFFFFFFFFu, cache_b = 0;
-    int s = 0;
-    while (t < t2 && s < NS) {
-        const float x = fmaf(t, dx, ox), y = fmaf(t, dy, oy), z = fmaf(t, dz, oz);
-        const float dt = calc_dt(m, t);
-        int nx, ny, nz;
-        float mip_bound;
-        if (probe<ONE_CASCADE>(m, bitfield, x, y, z, dt, nx, ny, nz, mip_bound, cache_bi, cache_b)) {
-            X[3 * s] = x; X[3 * s + 1] = y; X[3 * s + 2] = z;
-            D[3 * s] = dx; D[3 * s + 1] = dy; D[3 * s + 2] = dz;
-            TS[s] = t;
-            DT[s] = dt;
-            t += dt;
-            hits_t[2 * r] = t;
-            s++;
-        } else {
-            t = skip_voxel(m, t, x, y, z, dx, dy, dz, dxi, dyi, dzi, nx, ny, nz, mip_bound);
-        }
-    }
-    for (int k = s; k < NS; k++) {
-        X[3 * k] = 0.f; X[3 * k + 1] = 0.f; X[3 * k + 2] = 0.f;
-        D[3 * k] = 0.f; D[3 * k + 1] = 0.f; D[3 * k + 2] = 0.f;
-        TS[k] = 0.f;
-        DT[k] = 0.f;
-    }
-    n_eff[n] = s;
-}
-
-// ---------------------------------------------------------------------------------------------
-// ray_aabb_intersect (intersection.cu:5-56 + :95-97 sort): one lane per ray, voxels in order,
-// slots sorted stably by t1 (empty slots carry t1 = -1 and therefore sort first, as torch::sort does).
-template <int MAXH>
-__global__ __launch_bounds__(256) void ray_aabb_kernel(const float* __restrict__ rays_o,
-                                                       const float* __restrict__ rays_d, int64_t R,
-                                                       const float* __restrict__ centers,
-                                                       const float* __restrict__ half_sizes, int64_t V, int max_hits,
-                                                       int32_t* __restrict__ hit_cnt, float* __restrict__ hits_t,
-                                                       int64_t* __restrict__ hits_idx, float near_distance) {
-    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (r >= R) return;
-    float o[3] = {rays_o[3 * r], rays_o[3 * r + 1], rays_o[3 * r + 2]};
-    float inv[3] = {1.0f / rays_d[3 * r], 1.0f / rays_d[3 * r + 1], 1.0f / rays_d[3 * r + 2]};
-    float h1[MAXH], h2[MAXH];
-    int64_t hv[MAXH];
-#pragma unroll
-    for (int k = 0; k < MAXH; k++) { h1[k] = -1.0f; h2[k] = -1.0f; hv[k] = -1; }
-    int cnt = 0;
-    for (int64_t v = 0; v < V; v++) {
-        float a1[3], a2[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const float c = centers[3 * v + k], hs = half_sizes[3 * v + k];
-            const float tmin = (c - hs - o[k]) * inv[k];
-            const float tmax = (c + hs - o[k]) * inv[k];
-            a1[k] = fminf(tmin, tmax);
-            a2[k] = fmaxf(tmin, tmax);
-        }
-        float t1 = fmaxf(fmaxf(a1[0], a1[1]), a1[2]);
-        float t2 = fminf(fminf(a2[0], a2[1]), a2[2]);
-        if (t1 > t2) { t1 = -1.0f; t2 = -1.0f; }
-        if (t2 > 0) {
-            if (cnt < max_hits) {
-#pragma unroll
-                for (int k = 0; k < MAXH; k++)
-                    if (k == cnt) { h1[k] = fmaxf(t1, 0.0f); h2[k] = t2; hv[k] = v; }
-            }
-            cnt++;
-        }
-    }
-    // stable insertion sort of the max_hits slots by t1
-    for (int i = 1; i < max_hits; i++) {
-        for (int j = i; j > 0; j--) {
-            if (h1[j - 1] > h1[j]) {
-                float a = h1[j]; h1[j] = h1[j - 1]; h1[j - 1] = a;
-                float b = h2[j]; h2[j] = h2[j - 1]; h2[j - 1] = b;
-                int64_t c = hv[j]; hv[j] = hv[j - 1]; hv[j - 1] = c;
-            } else {
-                break;
-            }
-        }
-    }
-    hit_cnt[r] = cnt;
-    // render()'s near clamp of the first hit (rendering.py:28), fused: t1 in [0, near) -> near
-    if (h1[0] >= 0.0f && h1[0] < near_distance) h1[0] = near_distance;
-    for (int k = 0; k < max_hits; k++) {
-        hits_t[(r * max_hits + k) * 2] = h1[k];
-        hits_t[(r * max_hits + k) * 2 + 1] = h2[k];
-        hits_idx[r * max_hits + k] = hv[k];
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Compositing (volumerendering.cu:97-176 forward, :297-418 backward).  One wave per ray segment;
-// the segment's samples are taken in rows of 64 consecutive samples (lane l holds sample
-// row*64 + l, so every load is one contiguous 256-B piece), up to ROWS rows per round with all of
-// the round's loads issued before the first use.  Per row an inclusive DPP product scan of (1 - a)
-// gives the transmittance in front of each sample; the first sample whose transmittance after it
-// falls to T_threshold stops the ray (it is composited but not counted, quirk q6); the row's last
-// transmittance carries to the next row.  Every per-sample array is addressed through a buffer
-// descriptor sized to the ray's segment (buf_rsrc): lanes past N read 0 (so a = 0, 1 - a = 1 and
-// w = 0 fall out without masks) and their stores are dropped.  Per-ray values are scalar loads.
-
-// The ray handled by this wave and its segment.  The wave index is clamped instead of returning
-// early so the kernarg, rays_a and array-pointer loads issue as one scalar batch; `live` guards
-// the per-ray stores of the (at most 3) surplus waves of the last block.
-// Waves (rays) per workgroup of the compositors.
-#ifndef CF_WPB
-#define CF_WPB 4
-#endif
-struct RaySeg {
-    int64_t ray, start;
-    int N;
-    bool live;
-};
-__device__ __forceinline__ RaySeg load_ray_seg(const int64_t* __restrict__ rays_a, int64_t R, int blk) {
-    const int64_t n0 = __builtin_amdgcn_readfirstlane((int)(blk * CF_WPB + (threadIdx.x >> 6)));
-    const int64_t n = n0 < R ? n0 : R - 1;
-    RaySeg s;
-    s.ray = rays_a[3 * n];
-    s.start = rays_a[3 * n + 1];
-    s.N = (int)rays_a[3 * n + 2];
-    s.live = n0 < R;
-    return s;
-}
-
-// One block of a ray's rows (forward).  sigma/delta of every row of the block are loaded up front
-// (the transmittance needs only them), t/raw of rows 0-3 with them; the ROWS product scans run
-// interleaved in one asm (wave_incl_prod_multi) and only the carries chain through readlane; t/raw
-// of rows 4-7 (ROWS == 8) are fetched after rows 0-3 are accumulated (keeps the kernel at 8
-// waves/SIMD).  GUARD: rows past N are skipped (uniform branches).  Returns true when the ray
-// stopped in this block (quirk q6: the stopping sample is composited, not counted); the rest of the
-// segment then gets ws = 0 (volumerendering.cu:133 breaks, ws stays 0).
-// LOCAL (the single-wave path of rays longer than 256 samples, 4-row blocks): the chain starts at
-// Tc = 1 inside the block and is scaled by `carry` (the product of the preceding blocks) — the same
-// float operations, in the same order, as the one-workgroup path (composite_fw_coop), so a long ray
-// composites bit-identically on either path.
-template <int C, int ROWS, bool GUARD, bool LOCAL = false>
-__device__ __forceinline__ bool composite_fw_block(const __amdgpu_buffer_rsrc_t& r_s,
-                                                   const __amdgpu_buffer_rsrc_t& r_d,
-                                                   const __amdgpu_buffer_rsrc_t& r_t,
-                                                   const __amdgpu_buffer_rsrc_t& r_r,
-                                                   const __amdgpu_buffer_rsrc_t& r_w, int base, int N, float T_thr,
-                                                   int lane, float& Tc, float (&acc)[2 + C], int& total,
-                                                   float carry = 1.0f) {
-    constexpr int RT = ROWS < 4 ? ROWS : 4;
-    float sg[ROWS], dl[ROWS], tt[RT], rr[RT][C];
-#pragma unroll
-    for (int r = 0; r < ROWS; r++) {
-        const uint32_t k = (uint32_t)(base + r * 64 + lane);
-        if (!GUARD || r == 0 || base + r * 64 < N) {
-            sg[r] = buf_load(r_s, k * 4u);
-            dl[r] = buf_load(r_d, k * 4u);
-            if (r < RT) {
-                tt[r] = buf_load(r_t, k * 4u);
-#pragma unroll
-                for (int i = 0; i < C; i++) rr[r][i] = buf_load(r_r, k * (4u * C) + 4u * i);
-            }
-        } else {
-            sg[r] = dl[r] = 0.f;
-            if (r < RT) {
-                tt[r] = 0.f;
-#pragma unroll
-                for (int i = 0; i < C; i++) rr[r][i] = 0.f;
-            }
-        }
-    }
-    float a[ROWS], om[ROWS], p[ROWS];
-#pragma unroll
-    for (int r = 0; r < ROWS; r++) {
-        a[r] = 1.0f - __expf(-sg[r] * dl[r]);
-        om[r] = p[r] = 1.0f - a[r];
-    }
-    wave_incl_prod_multi<ROWS>(p);
-    // transmittance in front of (Tb) and after (Ta) each sample; lanes past N carry the last Ta
-    float Tb[ROWS];
-    uint64_t stopm[ROWS];
-#pragma unroll
-    for (int r = 0; r < ROWS; r++) {
-        Tb[r] = Tc * wave_shr1_dpp(p[r], 1.0f);
-        if constexpr (LOCAL) {
-            Tc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Tb[r] * om[r]), 63));
-            Tb[r] *= carry;
-            stopm[r] = __ballot(Tb[r] * om[r] <= T_thr);
-        } else {
-            const float Ta = Tb[r] * om[r];
-            stopm[r] = __ballot(Ta <= T_thr);
-            Tc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Ta), 63));
-        }
-    }
-    int srow = ROWS, slane = 64;  // first sample whose Ta <= T_thr (T is non-increasing)
-#pragma unroll
-    for (int r = ROWS - 1; r >= 0; r--)
-        if (stopm[r]) {
-            srow = r;
-            slane = __builtin_ctzll(stopm[r]);
-        }
-    float w[ROWS];
-#pragma unroll
-    for (int r = 0; r < ROWS; r++) {
-        w[r] = (r < srow || (r == srow && lane <= slane)) ? a[r] * Tb[r] : 0.f;
-        if (!GUARD || r == 0 || base + r * 64 < N) buf_store(r_w, (uint32_t)(base + r * 64 + lane) * 4u, w[r]);
-    }
-#pragma unroll
-    for (int r = 0; r < RT; r++) {
-        acc[0] += w[r];
-        acc[1] = fmaf(w[r], tt[r], acc[1]);
-#pragma unroll
-        for (int i = 0; i < C; i++) acc[2 + i] = fmaf(w[r], rr[r][i], acc[2 + i]);
-    }
-    if constexpr (ROWS > 4) {
-        if (base + 4 * 64 < N && srow >= 4) {
-            float t2[ROWS - 4], r2[ROWS - 4][C];
-#pragma unroll
-            for (int r = 4; r < ROWS; r++) {
-                const uint32_t k = (uint32_t)(base + r * 64 + lane);
-                if (base + r * 64 < N) {
-                    t2[r - 4] = buf_load(r_t, k * 4u);
-#pragma unroll
-                    for (int i = 0; i < C; i++) r2[r - 4][i] = buf_load(r_r, k * (4u * C) + 4u * i);
-                } else {
-                    t2[r - 4] = 0.f;
-#pragma unroll
-                    for (int i = 0; i < C; i++) r2[r - 4][i] = 0.f;
-                }
-            }
-#pragma unroll
-            for (int r = 4; r < ROWS; r++) {
-                acc[0] += w[r];
-                acc[1] = fmaf(w[r], t2[r - 4], acc[1]);
-#pragma unroll
-                for (int i = 0; i < C; i++) acc[2 + i] = fmaf(w[r], r2[r - 4][i], acc[2 + i]);
-            }
-        }
-    }
-    if (srow < ROWS) {
-        total = base + srow * 64 + slane;
-        for (int k = base + ROWS * 64 + lane; k < N; k += 64) buf_store(r_w, (uint32_t)k * 4u, 0.f);
-        return true;
-    }
-    return false;
-}
-
-// Forward (volumerendering.cu:97-176): a ray with N <= 256 samples is one block of 1, 2 or 4 rows
-// (every row non-empty: no guards), a longer one runs in guarded blocks of 8 rows.
-// Long rays (CF_LONG < N <= CF_COOP_MAX samples) are taken by a whole workgroup: wave v composites
-// the ray's samples [256 v, 256 v + 256) as one 4-row block with a local carry of 1, the waves'
-// segment products meet in LDS (carry-in = product of the preceding waves' products), the first
-// stopping sample over the ray is the minimum of the waves' first stops, and the per-wave sums are
-// added in wave order.  Every load of the ray is issued in ONE round (a single wave needs 2-4
-// dependent rounds for 256 < N <= 1024, the tail that bounded the launch); 3 LDS barriers.  The
-// training step's rows hold the long rays first (march_train_place), so workgroup j < n_coop takes
-// row j when it is long; long rays outside the first n_coop rows (eager callers: rows in ray order)
-// stay on the single-wave path.  Float order: T = carry x local prefix (vs one chained product),
-// within the compositor's scan tolerance.
-#define CF_LONG 256
-#define CF_COOP_MAX (256 * CF_WPB)
-// The n_coop workgroups at the front of the grid walk the rows b, b + n_coop, ... and stop at the
-// first short one (N <= CF_LONG): with the long rays first, every long ray is taken whatever their
-// number.  (Rows with N > CF_COOP_MAX are passed over and stay single-wave.)  Row `row` (long) is
-// taken by a workgroup iff no row row - k * n_coop (k >= 1) is short.  Successive rows of one
-// workgroup reuse its LDS without an extra barrier: every LDS array is read between the barriers
-// of its own row, before the next row writes it behind a later barrier.
-__device__ __forceinline__ bool cf_coop_takes(const int64_t* __restrict__ rays_a, int64_t row, int n_coop) {
-    for (int64_t k = row - n_coop; k >= 0; k -= n_coop)
-        if (rays_a[3 * k + 2] <= CF_LONG) return false;
-    return true;
-}
-template <int C>
-__device__ __forceinline__ void composite_fw_coop(const float* __restrict__ sigmas, const float* __restrict__ raws,
-                                                  const float* __restrict__ deltas, const float* __restrict__ ts,
-                                                  const int64_t* __restrict__ rays_a, int64_t row, float T_thr,
-                                                  int64_t* __restrict__ total_samples, float* __restrict__ opacity,
-                                                  float* __restrict__ depth, float* __restrict__ rend,
-                                                  float* __restrict__ ws, float bg, float* __restrict__ rgb_bg) {
-    __shared__ float sP[CF_WPB];
-    __shared__ int sStop[CF_WPB];
-    __shared__ float sAcc[CF_WPB][2 + C];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t ray = rays_a[3 * row], start = rays_a[3 * row + 1];
-    const int N = (int)rays_a[3 * row + 2];
-    if (N <= CF_LONG || N > CF_COOP_MAX) return;  // workgroup-uniform: no wave reaches a barrier
-    const uint32_t nb = (uint32_t)N * 4u;
-    const auto r_s = buf_rsrc(sigmas + start, nb), r_d = buf_rsrc(deltas + start, nb);
-    const auto r_t = buf_rsrc(ts + start, nb), r_r = buf_rsrc(raws + start * C, nb * C);
-    const auto r_w = buf_rsrc(ws + start, nb);
-    const int base = wv * 256;
-    float sg[4], dl[4], tt[4], rr[4][C];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {  // past N (and whole waves past N) the descriptors read 0
-        const uint32_t k = (uint32_t)(base + r * 64 + lane);
-        sg[r] = buf_load(r_s, k * 4u);
-        dl[r] = buf_load(r_d, k * 4u);
-        tt[r] = buf_load(r_t, k * 4u);
-#pragma unroll
-        for (int i = 0; i < C; i++) rr[r][i] = buf_load(r_r, k * (4u * C) + 4u * i);
-    }
-    float a[4], om[4], p[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        a[r] = 1.0f - __expf(-sg[r] * dl[r]);
-        om[r] = p[r] = 1.0f - a[r];
-    }
-    wave_incl_prod_multi<4>(p);
-    float Tb[4], Tc = 1.0f;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        Tb[r] = Tc * wave_shr1_dpp(p[r], 1.0f);
-        Tc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Tb[r] * om[r]), 63));
-    }
-    if (lane == 0) sP[wv] = Tc;
-    __syncthreads();
-    float carry = 1.0f;
-    for (int v = 0; v < wv; v++) carry *= sP[v];
-    int stop = INT_MAX;  // first sample (ray position) whose transmittance after it is <= T_thr
-#pragma unroll
-    for (int r = 3; r >= 0; r--) {
-        Tb[r] *= carry;
-        const uint64_t m = __ballot(Tb[r] * om[r] <= T_thr);
-        if (m) stop = base + r * 64 + __builtin_ctzll(m);
-    }
-    if (lane == 0) sStop[wv] = stop;
-    __syncthreads();
-#pragma unroll
-    for (int v = 0; v < CF_WPB; v++) stop = min(stop, sStop[v]);
-    float acc[2 + C];
-#pragma unroll
-    for (int i = 0; i < 2 + C; i++) acc[i] = 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int pos = base + r * 64 + lane;
-        const float w = pos <= stop ? a[r] * Tb[r] : 0.f;  // the stopping sample is composited (q6)
-        if (base + r * 64 < N) buf_store(r_w, (uint32_t)pos * 4u, w);
-        acc[0] += w;
-        acc[1] = fmaf(w, tt[r], acc[1]);
-#pragma unroll
-        for (int i = 0; i < C; i++) acc[2 + i] = fmaf(w, rr[r][i], acc[2 + i]);
-    }
-    wave_sum_multi<2 + C>(acc);
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 2 + C; i++) sAcc[wv][i] = acc[i];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int i = 0; i < 2 + C; i++) {
-            float t = sAcc[0][i];
-            for (int v = 1; v < CF_WPB; v++) t += sAcc[v][i];
-            acc[i] = t;
-        }
-        opacity[ray] = acc[0];
-        depth[ray] = acc[1];
-#pragma unroll
-        for (int i = 0; i < C; i++) rend[ray * C + i] = acc[2 + i];
-        if (rgb_bg) {
-#pragma unroll
-            for (int i = 0; i < C; i++) rgb_bg[ray * C + i] = acc[2 + i] + bg * (1 - acc[0]);
-        }
-        total_samples[ray] = stop == INT_MAX ? N : stop;
-    }
-}
-
-template <int C>
-__global__ __launch_bounds__(64 * CF_WPB) void composite_fw_kernel(
-    const float* __restrict__ sigmas, const float* __restrict__ raws, const float* __restrict__ deltas,
-    const float* __restrict__ ts, const int64_t* __restrict__ rays_a, int64_t R, float T_thr,
-    int64_t* __restrict__ total_samples, float* __restrict__ opacity, float* __restrict__ depth,
-    float* __restrict__ rend, float* __restrict__ ws, float bg, float* __restrict__ rgb_bg, int n_coop) {
-    if ((int)blockIdx.x < n_coop) {
-        for (int64_t row = blockIdx.x; row < R; row += n_coop) {  // (LDS reuse: see cf_coop_takes)
-            const int N = (int)rays_a[3 * row + 2];
-            if (N <= CF_LONG) break;
-            composite_fw_coop<C>(sigmas, raws, deltas, ts, rays_a, row, T_thr, total_samples, opacity, depth, rend,
-                                 ws, bg, rgb_bg);
-        }
-        return;
-    }
-    const int lane = threadIdx.x & 63;
-    const RaySeg g = load_ray_seg(rays_a, R, (int)blockIdx.x - n_coop);
-    const int N = g.N;
-    const int64_t row = __builtin_amdgcn_readfirstlane((int)((blockIdx.x - n_coop) * CF_WPB + (threadIdx.x >> 6)));
-    if (N > CF_LONG && N <= CF_COOP_MAX && cf_coop_takes(rays_a, row, n_coop)) return;  // (wave-uniform)
-    const uint32_t nb = (uint32_t)N * 4u;
-    const auto r_s = buf_rsrc(sigmas + g.start, nb), r_d = buf_rsrc(deltas + g.start, nb);
-    const auto r_t = buf_rsrc(ts + g.start, nb), r_r = buf_rsrc(raws + g.start * C, nb * C);
-    const auto r_w = buf_rsrc(ws + g.start, nb);
-    float Tc = 1.0f;
-    float acc[2 + C];  // opacity, depth, rend[C]
-#pragma unroll
-    for (int i = 0; i < 2 + C; i++) acc[i] = 0.f;
-    int total = N;
-    if (N <= 64) {  // N == 0 included: every load reads 0, every store is dropped
-        composite_fw_block<C, 1, false>(r_s, r_d, r_t, r_r, r_w, 0, N, T_thr, lane, Tc, acc, total);
-    } else if (N <= 128) {
-        composite_fw_block<C, 2, false>(r_s, r_d, r_t, r_r, r_w, 0, N, T_thr, lane, Tc, acc, total);
-    } else if (N <= 256) {
-        composite_fw_block<C, 4, false>(r_s, r_d, r_t, r_r, r_w, 0, N, T_thr, lane, Tc, acc, total);
-    } else {  // 4-row blocks with local chains, block sums added in order (as composite_fw_coop)
-        float carry = 1.0f;
-        for (int base = 0; base < N; base += 4 * 64) {
-            float bacc[2 + C];
-#pragma unroll
-            for (int i = 0; i < 2 + C; i++) bacc[i] = 0.f;
-            Tc = 1.0f;
-            const bool stopped =
-                composite_fw_block<C, 4, true, true>(r_s, r_d, r_t, r_r, r_w, base, N, T_thr, lane, Tc, bacc, total, carry);
-            wave_sum_multi<2 + C>(bacc);
-#pragma unroll
-            for (int i = 0; i < 2 + C; i++) acc[i] += bacc[i];
-            carry *= Tc;
-            if (stopped) break;
-        }
-    }
-    if (N <= 256) wave_sum_multi<2 + C>(acc);
-    if (g.live && lane == 0) {
-        opacity[g.ray] = acc[0];
-        depth[g.ray] = acc[1];
-#pragma unroll
-        for (int i = 0; i < C; i++) rend[g.ray * C + i] = acc[2 + i];
-        if (rgb_bg) {  // render()'s background, rendering.py:232-240: rgb = rend + bg * (1 - opacity)
-#pragma unroll
-            for (int i = 0; i < C; i++) rgb_bg[g.ray * C + i] = acc[2 + i] + bg * (1 - acc[0]);
-        }
-        total_samples[g.ray] = total;
-    }
-}
-
-// Backward, one block of a ray's rows (volumerendering.cu:297-364).  T is the post-update
-// transmittance (quirk q10); d/r are inclusive prefix sums of w*t and w*raw; (sum - pre[s]) is the
-// suffix of dL_dws*ws over the WHOLE marched segment (:331-335).  Evaluation order of dL_dsigmas
-// follows :349-359.  All of the block's loads are issued up front; the product scans run
-// interleaved, the prefix sums of (w*t, w*raw_0..2) as one 4-way DPP scan per row; carries chain
-// through readlane.  DWS: a non-NULL dL_dws (the reference's is a zero tensor in training, q5).
-template <int C, int ROWS, bool GUARD, bool DWS>
-__device__ __forceinline__ bool composite_bw_block(
-    const __amdgpu_buffer_rsrc_t& r_s, const __amdgpu_buffer_rsrc_t& r_d, const __amdgpu_buffer_rsrc_t& r_t,
-    const __amdgpu_buffer_rsrc_t& r_r, const __amdgpu_buffer_rsrc_t& r_dw, const __amdgpu_buffer_rsrc_t& r_ws,
-    const __amdgpu_buffer_rsrc_t& r_gs, const __amdgpu_buffer_rsrc_t& r_gr, int base, int N, float T_thr,
-    int lane, float gO, float dD, float D, float tot, const float (&dR)[C], const float (&RE)[C], float& Tc,
-    float& cd, float& cpw, float (&cr)[C]) {
-    float sg[ROWS], dl[ROWS], tt[ROWS], rr[ROWS][C], dws[ROWS], pw[ROWS];
-#pragma unroll
-    for (int r = 0; r < ROWS; r++) {
-        const uint32_t k = (uint32_t)(base + r * 64 + lane);
-        if (!GUARD || r == 0 || base + r * 64 < N) {
-            sg[r] = buf_load(r_s, k * 4u);
-            dl[r] = buf_load(r_d, k * 4u);
-            tt[r] = buf_load(r_t, k * 4u);
-#pragma unroll
-            for (int i = 0; i < C; i++) rr[r][i] = buf_load(r_r, k * (4u * C) + 4u * i);
-            dws[r] = DWS ? buf_load(r_dw, k * 4u) : 0.f;
-            pw[r] = DWS ? dws[r] * buf_load(r_ws, k * 4u) : 0.f;
-        } else {
-            sg[r] = dl[r] = tt[r] = dws[r] = pw[r] = 0.f;
-#pragma unroll
-            for (int i = 0; i < C; i++) rr[r][i] = 0.f;
-        }
-    }
-    float a[ROWS], om[ROWS], p[ROWS];
-#pragma unroll
-    for (int r = 0; r < ROWS; r++) {
-        a[r] = 1.0f - __expf(-sg[r] * dl[r]);
-        om[r] = p[r] = 1.0f - a[r];
-    }
-    wave_incl_prod_multi<ROWS>(p);
-    float Tb[ROWS], Ta[ROWS];
-    uint64_t stopm[ROWS];
-#pragma unroll
-    for (int r = 0; r < ROWS; r++) {
-        Tb[r] = Tc * wave_shr1_dpp(p[r], 1.0f);
-        Ta[r] = Tb[r] * om[r];
-        stopm[r] = __ballot(Ta[r] <= T_thr);
-        Tc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Ta[r]), 63));
-    }
-    int srow = ROWS, slane = 64;
-#pragma unroll
-    for (int r = ROWS - 1; r >= 0; r--)
-        if (stopm[r]) {
-            srow = r;
-            slane = __builtin_ctzll(stopm[r]);
-        }
-#pragma unroll
-    for (int r = 0; r < ROWS; r++) {
-        const bool inc = r < srow || (r == srow && lane <= slane);
-        const float w = inc ? a[r] * Tb[r] : 0.f;
-        // inclusive prefixes (this row + carry) of w*t, w*raw_i, dL_dws*ws
-        float run_d = w * tt[r], run_r[C];
-#pragma unroll
-        for (int i = 0; i < C; i++) run_r[i] = w * rr[r][i];
-        if constexpr (C == 3) {
-            wave_incl_sum4(run_d, run_r[0], run_r[1], run_r[2]);
-        } else {
-            run_d = wave_incl_sum_dpp(run_d);
-#pragma unroll
-            for (int i = 0; i < C; i++) run_r[i] = wave_incl_sum_dpp(run_r[i]);
-        }
-        run_d += cd;
-#pragma unroll
-        for (int i = 0; i < C; i++) run_r[i] += cr[i];
-        const float run_pw = DWS ? cpw + wave_incl_sum_dpp(pw[r]) : 0.f;
-        float gs = gO + dD * (tt[r] * Ta[r] - (D - run_d)) + Ta[r] * dws[r] - (tot - run_pw);
-        const bool live_row = !GUARD || r == 0 || base + r * 64 < N;
-#pragma unroll
-        for (int i = 0; i < C; i++) {
-            gs += dR[i] * (rr[r][i] * Ta[r] - (RE[i] - run_r[i]));
-            if (live_row) buf_store(r_gr, (uint32_t)(base + r * 64 + lane) * (4u * C) + 4u * i, dR[i] * w);
-        }
-        if (live_row) buf_store(r_gs, (uint32_t)(base + r * 64 + lane) * 4u, inc ? gs * dl[r] : 0.f);
-        cd = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(run_d), 63));
-        if (DWS) cpw = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(run_pw), 63));
-#pragma unroll
-        for (int i = 0; i < C; i++) cr[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(run_r[i]), 63));
-    }
-    if (srow < ROWS) {  // rest of the segment: zero gradients
-        for (int k = base + ROWS * 64 + lane; k < N; k += 64) {
-            buf_store(r_gs, (uint32_t)k * 4u, 0.f);
-#pragma unroll
-            for (int i = 0; i < C; i++) buf_store(r_gr, (uint32_t)k * (4u * C) + 4u * i, 0.f);
-        }
-        return true;
-    }
-    return false;
-}
-
-// Backward (volumerendering.cu:297-418): same block structure as the forward (1/2/4-row blocks for
-// N <= 256, guarded 4-row blocks beyond).  A NULL upstream gradient skips its term.
-template <int C, bool DWS>
-__device__ __forceinline__ void composite_bw_ray(
-    const float* __restrict__ dL_dopacity, const float* __restrict__ dL_ddepth, const float* __restrict__ dL_drend,
-    const float* __restrict__ dL_dws, const float* __restrict__ sigmas, const float* __restrict__ raws,
-    const float* __restrict__ ws, const float* __restrict__ deltas, const float* __restrict__ ts, const RaySeg& g,
-    const float* __restrict__ opacity, const float* __restrict__ depth, const float* __restrict__ rend,
-    float T_thr, float* __restrict__ dL_dsigmas, float* __restrict__ dL_draws, float bg) {
-    const int lane = threadIdx.x & 63;
-    const int N = g.N;
-    const int64_t ray = g.ray;
-    const float dO = dL_dopacity ? dL_dopacity[ray] : 0.f;
-    const float dD = dL_ddepth ? dL_ddepth[ray] : 0.f;
-    const float O = opacity[ray], D = depth[ray];
-    float dR[C], RE[C];
-#pragma unroll
-    for (int i = 0; i < C; i++) {
-        dR[i] = dL_drend ? dL_drend[ray * C + i] : 0.f;
-        RE[i] = rend[ray * C + i];
-    }
-    // with the background folded in (rgb = rend + bg * (1 - O)): dL/drend = dL/drgb and the opacity
-    // picks up -bg * sum_i dL/drgb_i (the reference's autograd through rendering.py:236)
-    float dOe = dO;
-    if (bg != 0.f) {
-#pragma unroll
-        for (int i = 0; i < C; i++) dOe -= bg * dR[i];
-    }
-    const float gO = dOe * (1 - O);
-    const uint32_t nb = (uint32_t)N * 4u;
-    const auto r_s = buf_rsrc(sigmas + g.start, nb), r_d = buf_rsrc(deltas + g.start, nb);
-    const auto r_t = buf_rsrc(ts + g.start, nb), r_r = buf_rsrc(raws + g.start * C, nb * C);
-    const auto r_gs = buf_rsrc(dL_dsigmas + g.start, nb), r_gr = buf_rsrc(dL_draws + g.start * C, nb * C);
-    const auto r_dw = buf_rsrc(DWS ? dL_dws + g.start : dL_dsigmas, DWS ? nb : 0u);
-    const auto r_ws = buf_rsrc(DWS ? ws + g.start : dL_dsigmas, DWS ? nb : 0u);
-    float tot = 0.f;  // sum of dL_dws * ws over the whole segment
-    if (DWS) {
-        for (int k = lane; k < N; k += 64) tot = fmaf(buf_load(r_dw, k * 4u), buf_load(r_ws, k * 4u), tot);
-        tot = wave_sum_dpp(tot);
-    }
-    float Tc = 1.0f, cd = 0.f, cpw = 0.f, cr[C];
-#pragma unroll
-    for (int i = 0; i < C; i++) cr[i] = 0.f;
-#define NCN_BW_BLOCK(ROWS, GUARD, BASE)                                                                    \
-    composite_bw_block<C, ROWS, GUARD, DWS>(r_s, r_d, r_t, r_r, r_dw, r_ws, r_gs, r_gr, BASE, N, T_thr, lane, gO, \
-                                            dD, D, tot, dR, RE, Tc, cd, cpw, cr)
-    if (N <= 64) {
-        NCN_BW_BLOCK(1, false, 0);
-    } else if (N <= 128) {
-        NCN_BW_BLOCK(2, false, 0);
-    } else if (N <= 256) {
-        NCN_BW_BLOCK(4, false, 0);
-    } else {
-        for (int base = 0; base < N; base += 4 * 64)
-            if (NCN_BW_BLOCK(4, true, base)) break;
-    }
-#undef NCN_BW_BLOCK
-}
-
-// Long rays in the backward: one workgroup per ray as in the forward.  Phase 1: every wave loads
-// its 256 samples and publishes its local transmittance product and its local sums of w*t, w*raw
-// (w with a carry-in of 1) and dL_dws*ws; after one barrier wave v has the carries of the waves in
-// front of it (T_in = product of their products; prefix sums = their sums scaled by their T_in;
-// the stop cannot lie in front of the first stopping wave, so their sums are uncut), finds its
-// first stop, and after a second barrier the ray's first stop cuts w as in the single-wave rows.
-template <int C, bool DWS>
-__device__ __forceinline__ void composite_bw_coop(
-    const float* __restrict__ dL_dopacity, const float* __restrict__ dL_ddepth, const float* __restrict__ dL_drend,
-    const float* __restrict__ dL_dws, const float* __restrict__ sigmas, const float* __restrict__ raws,
-    const float* __restrict__ ws, const float* __restrict__ deltas, const float* __restrict__ ts,
-    const int64_t* __restrict__ rays_a, int64_t row, const float* __restrict__ opacity,
-    const float* __restrict__ depth, const float* __restrict__ rend, float T_thr, float* __restrict__ dL_dsigmas,
-    float* __restrict__ dL_draws, float bg) {
-    __shared__ float sS[CF_WPB][3 + C];  // product, sum w*t, sum dL_dws*ws, sums w*raw
-    __shared__ int sStop[CF_WPB];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t ray = rays_a[3 * row], start = rays_a[3 * row + 1];
-    const int N = (int)rays_a[3 * row + 2];
-    if (N <= CF_LONG || N > CF_COOP_MAX) return;  // workgroup-uniform
-    const float dO = dL_dopacity ? dL_dopacity[ray] : 0.f;
-    const float dD = dL_ddepth ? dL_ddepth[ray] : 0.f;
-    const float O = opacity[ray], D = depth[ray];
-    float dR[C], RE[C];
-#pragma unroll
-    for (int i = 0; i < C; i++) {
-        dR[i] = dL_drend ? dL_drend[ray * C + i] : 0.f;
-        RE[i] = rend[ray * C + i];
-    }
-    float dOe = dO;
-    if (bg != 0.f) {
-#pragma unroll
-        for (int i = 0; i < C; i++) dOe -= bg * dR[i];
-    }
-    const float gO = dOe * (1 - O);
-    const uint32_t nb = (uint32_t)N * 4u;
-    const auto r_s = buf_rsrc(sigmas + start, nb), r_d = buf_rsrc(deltas + start, nb);
-    const auto r_t = buf_rsrc(ts + start, nb), r_r = buf_rsrc(raws + start * C, nb * C);
-    const auto r_gs = buf_rsrc(dL_dsigmas + start, nb), r_gr = buf_rsrc(dL_draws + start * C, nb * C);
-    const auto r_dw = buf_rsrc(DWS ? dL_dws + start : dL_dsigmas, DWS ? nb : 0u);
-    const auto r_ws = buf_rsrc(DWS ? ws + start : dL_dsigmas, DWS ? nb : 0u);
-    const int base = wv * 256;
-    float sg[4], dl[4], tt[4], rr[4][C], dws[4], pw[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const uint32_t k = (uint32_t)(base + r * 64 + lane);
-        sg[r] = buf_load(r_s, k * 4u);
-        dl[r] = buf_load(r_d, k * 4u);
-        tt[r] = buf_load(r_t, k * 4u);
-#pragma unroll
-        for (int i = 0; i < C; i++) rr[r][i] = buf_load(r_r, k * (4u * C) + 4u * i);
-        dws[r] = DWS ? buf_load(r_dw, k * 4u) : 0.f;
-        pw[r] = DWS ? dws[r] * buf_load(r_ws, k * 4u) : 0.f;
-    }
-    float a[4], om[4], p[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        a[r] = 1.0f - __expf(-sg[r] * dl[r]);
-        om[r] = p[r] = 1.0f - a[r];
-    }
-    wave_incl_prod_multi<4>(p);
-    float Tb[4], Tl = 1.0f, ls[2 + C];  // local sums: w*t, dL_dws*ws, w*raw
-#pragma unroll
-    for (int i = 0; i < 2 + C; i++) ls[i] = 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        Tb[r] = Tl * wave_shr1_dpp(p[r], 1.0f);
-        Tl = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Tb[r] * om[r]), 63));
-        const float w = a[r] * Tb[r];
-        ls[0] = fmaf(w, tt[r], ls[0]);
-        ls[1] += pw[r];
-#pragma unroll
-        for (int i = 0; i < C; i++) ls[2 + i] = fmaf(w, rr[r][i], ls[2 + i]);
-    }
-    wave_sum_multi<2 + C>(ls);
-    if (lane == 0) {
-        sS[wv][0] = Tl;
-#pragma unroll
-        for (int i = 0; i < 2 + C; i++) sS[wv][1 + i] = ls[i];
-    }
-    __syncthreads();
-    float Tc = 1.0f, cd = 0.f, cpw = 0.f, tot = 0.f, cr[C];
-#pragma unroll
-    for (int i = 0; i < C; i++) cr[i] = 0.f;
-    for (int v = 0; v < CF_WPB; v++) {
-        if (v < wv) {
-            cd = fmaf(Tc, sS[v][1], cd);
-            cpw += sS[v][2];
-#pragma unroll
-            for (int i = 0; i < C; i++) cr[i] = fmaf(Tc, sS[v][3 + i], cr[i]);
-            Tc *= sS[v][0];
-        }
-        tot += sS[v][2];
-    }
-    int stop = INT_MAX;
-    float Ta[4];
-#pragma unroll
-    for (int r = 3; r >= 0; r--) {
-        Tb[r] *= Tc;
-        Ta[r] = Tb[r] * om[r];
-        const uint64_t m = __ballot(Ta[r] <= T_thr);
-        if (m) stop = base + r * 64 + __builtin_ctzll(m);
-    }
-    if (lane == 0) sStop[wv] = stop;
-    __syncthreads();
-#pragma unroll
-    for (int v = 0; v < CF_WPB; v++) stop = min(stop, sStop[v]);
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int pos = base + r * 64 + lane;
-        const bool inc = pos <= stop;
-        const float w = inc ? a[r] * Tb[r] : 0.f;
-        float run_d = w * tt[r], run_r[C];
-#pragma unroll
-        for (int i = 0; i < C; i++) run_r[i] = w * rr[r][i];
-        if constexpr (C == 3) {
-            wave_incl_sum4(run_d, run_r[0], run_r[1], run_r[2]);
-        } else {
-            run_d = wave_incl_sum_dpp(run_d);
-#pragma unroll
-            for (int i = 0; i < C; i++) run_r[i] = wave_incl_sum_dpp(run_r[i]);
-        }
-        run_d += cd;
-#pragma unroll
-        for (int i = 0; i < C; i++) run_r[i] += cr[i];
-        const float run_pw = DWS ? cpw + wave_incl_sum_dpp(pw[r]) : 0.f;
-        float gs = gO + dD * (tt[r] * Ta[r] - (D - run_d)) + Ta[r] * dws[r] - (tot - run_pw);
-        const bool live_row = base + r * 64 < N;
-#pragma unroll
-        for (int i = 0; i < C; i++) {
-            gs += dR[i] * (rr[r][i] * Ta[r] - (RE[i] - run_r[i]));
-            if (live_row) buf_store(r_gr, (uint32_t)pos * (4u * C) + 4u * i, dR[i] * w);
-        }
-        if (live_row) buf_store(r_gs, (uint32_t)pos * 4u, inc ? gs * dl[r] : 0.f);
-        cd = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(run_d), 63));
-        if (DWS) cpw = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(run_pw), 63));
-#pragma unroll
-        for (int i = 0; i < C; i++) cr[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(run_r[i]), 63));
-    }
-}
-
-// (composite_bw_kernel_nodws takes 80 VGPRs at C = 3: 6 waves/SIMD.  Measured with forced 7 / 8
-// waves per SIMD (tools/composite_bw_probe.py, 8192 marched rays): 9.9-10.0 / 10.3-10.5 us against
-// 9.6 — spills.)
-template <int C>
-__global__ __launch_bounds__(64 * CF_WPB) void composite_bw_kernel_nodws(
-    const float* __restrict__ dL_dopacity, const float* __restrict__ dL_ddepth, const float* __restrict__ dL_drend,
-    const float* __restrict__ dL_dws, const float* __restrict__ sigmas, const float* __restrict__ raws,
-    const float* __restrict__ ws, const float* __restrict__ deltas, const float* __restrict__ ts,
-    const int64_t* __restrict__ rays_a, int64_t R, const float* __restrict__ opacity,
-    const float* __restrict__ depth, const float* __restrict__ rend, float T_thr, float* __restrict__ dL_dsigmas,
-    float* __restrict__ dL_draws, float bg, int n_coop) {
-    if ((int)blockIdx.x < n_coop) {
-        for (int64_t row = blockIdx.x; row < R; row += n_coop) {
-            if ((int)rays_a[3 * row + 2] <= CF_LONG) break;
-            composite_bw_coop<C, false>(dL_dopacity, dL_ddepth, dL_drend, dL_dws, sigmas, raws, ws, deltas, ts,
-                                       rays_a, row, opacity, depth, rend, T_thr, dL_dsigmas, dL_draws, bg);
-        }
-        return;
-    }
-    const RaySeg g = load_ray_seg(rays_a, R, (int)blockIdx.x - n_coop);
-    const int64_t row = __builtin_amdgcn_readfirstlane((int)((blockIdx.x - n_coop) * CF_WPB + (threadIdx.x >> 6)));
-    if (g.N > CF_LONG && g.N <= CF_COOP_MAX && cf_coop_takes(rays_a, row, n_coop)) return;
-    composite_bw_ray<C, false>(dL_dopacity, dL_ddepth, dL_drend, dL_dws, sigmas, raws, ws, deltas, ts, g, opacity,
-                               depth, rend, T_thr, dL_dsigmas, dL_draws, bg);
-}
-template <int C>
-__global__ __launch_bounds__(64 * CF_WPB) void composite_bw_kernel_dws(
-    const float* __restrict__ dL_dopacity, const float* __restrict__ dL_ddepth, const float* __restrict__ dL_drend,
-    const float* __restrict__ dL_dws, const float* __restrict__ sigmas, const float* __restrict__ raws,
-    const float* __restrict__ ws, const float* __restrict__ deltas, const float* __restrict__ ts,
-    const int64_t* __restrict__ rays_a, int64_t R, const float* __restrict__ opacity,
-    const float* __restrict__ depth, const float* __restrict__ rend, float T_thr, float* __restrict__ dL_dsigmas,
-    float* __restrict__ dL_draws, float bg, int n_coop) {
-    if ((int)blockIdx.x < n_coop) {
-        for (int64_t row = blockIdx.x; row < R; row += n_coop) {
-            if ((int)rays_a[3 * row + 2] <= CF_LONG) break;
-            composite_bw_coop<C, true>(dL_dopacity, dL_ddepth, dL_drend, dL_dws, sigmas, raws, ws, deltas, ts,
-                                       rays_a, row, opacity, depth, rend, T_thr, dL_dsigmas, dL_draws, bg);
-        }
-        return;
-    }
-    const RaySeg g = load_ray_seg(rays_a, R, (int)blockIdx.x - n_coop);
-    const int64_t row = __builtin_amdgcn_readfirstlane((int)((blockIdx.x - n_coop) * CF_WPB + (threadIdx.x >> 6)));
-    if (g.N > CF_LONG && g.N <= CF_COOP_MAX && cf_coop_takes(rays_a, row, n_coop)) return;
-    composite_bw_ray<C, true>(dL_dopacity, dL_ddepth, dL_drend, dL_dws, sigmas, raws, ws, deltas, ts, g, opacity,
-                              depth, rend, T_thr, dL_dsigmas, dL_draws, bg);
-}
-
-// composite_test_multi_fw (volumerendering.cu:504-550): lane per alive ray, serial (test path).
-// offsets (ncn_composite_test_fw_compact): NULL, or the start of ray n's samples in compacted
-// sigmas / raws (ncn_test_compact); deltas / ts stay in the marcher's (alive, NS) layout.
-__global__ __launch_bounds__(256) void composite_test_kernel(const float* __restrict__ sigmas,
-                                                             const float* __restrict__ raws,
-                                                             const float* __restrict__ deltas,
-                                                             const float* __restrict__ ts, int64_t* __restrict__ alive,
-                                                             int64_t A, int NS, int C, float T_thr,
-                                                             const int32_t* __restrict__ n_eff,
-                                                             float* __restrict__ opacity, float* __restrict__ depth,
-                                                             float* __restrict__ rend,
-                                                             const int32_t* __restrict__ offsets,
-                                                             const int32_t* __restrict__ ctrl) {
-    if (ctrl) {
-        A = ctrl[0];
-        NS = ctrl[1];
-    }
-    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (n >= A) return;
-    if (n_eff[n] == 0) {
-        alive[n] = -1;
-        return;
-    }
-    const int64_t r = alive[n];
-    const int64_t base = offsets ? (int64_t)offsets[n] : n * (int64_t)NS;
-    float T = 1.0f - opacity[r];
-    for (int s = 0; s < n_eff[n]; s++) {
-        const int64_t k = n * (int64_t)NS + s, kc = base + s;
-        const float a = 1.0f - __expf(-sigmas[kc] * deltas[k]);
-        const float w = a * T;
-        for (int i = 0; i < C; i++) rend[r * C + i] = fmaf(w, raws[kc * C + i], rend[r * C + i]);
-        depth[r] = fmaf(w, ts[k], depth[r]);
-        opacity[r] += w;
-        T *= 1.0f - a;
-        if (T <= T_thr) {
-            alive[n] = -1;
-            break;
-        }
-    }
-}
-
-// Compaction of the test marcher's output (the fused test-render iteration): the valid samples of
-// every alive ray (its first n_eff of NS slots) copied to consecutive rows of xyz_c / dir_c, ray n's
-// rows starting at offsets[n]; count[0] = the total.  A workgroup scans its 256 rays' n_eff and
-// reserves its rows with one atomic on count, so the workgroups' order in the output is arbitrary
-// (the compositor reads through offsets; the field's arithmetic is per sample).  count must be 0.
-__global__ __launch_bounds__(256) void test_compact_kernel(const float* __restrict__ xyzs,
-                                                           const float* __restrict__ dirs,
-                                                           const int32_t* __restrict__ n_eff, int64_t A, int NS,
-                                                           int32_t* __restrict__ offsets, float* __restrict__ xyz_c,
-                                                           float* __restrict__ dir_c, int32_t* __restrict__ count) {
-    __shared__ int wsum[4];
-    __shared__ int base;
-    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int c = n < A ? n_eff[n] : 0;
-    int incl = c;  // wave inclusive scan
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) wsum[wid] = incl;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int tot = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        base = tot ? atomicAdd(count, tot) : 0;
-    }
-    __syncthreads();
-    int pre = base;
-    for (int w = 0; w < wid; w++) pre += wsum[w];
-    const int off = pre + incl - c;
-    if (n >= A) return;
-    offsets[n] = off;
-    const float* X = xyzs + n * (int64_t)NS * 3;
-    const float* D = dirs + n * (int64_t)NS * 3;
-    for (int s = 0; s < c; s++) {
-        const int64_t o = (int64_t)(off + s) * 3;
-        xyz_c[o] = X[3 * s]; xyz_c[o + 1] = X[3 * s + 1]; xyz_c[o + 2] = X[3 * s + 2];
-        dir_c[o] = D[3 * s]; dir_c[o + 1] = D[3 * s + 1]; dir_c[o + 2] = D[3 * s + 2];
-    }
-}
-
-// Device-driven test loop (rendering.py:68-105 without a host read per iteration): ctrl (int32) =
-// {0 alive rays A, 1 samples per ray NS, 2 samples so far, 3 done, 4 valid samples of the iteration,
-//  5 next alive count, 6 iterations run, 7 alive x NS summed}.  After the compositor: the rays it
-// kept (alive >= 0) are compacted into alive_next (order irrelevant: every ray is independent) and
-// one thread forms the next iteration exactly as the reference's loop head does — stop when no ray
-// is alive or samples >= max_samples, else NS = max(min(n_rays / A, 64), min_samples).  A done loop
-// has A = 0, so further iterations launch empty.
-// Block-range compaction for the device test loop: workgroup b owns a contiguous range of the
-// A items (a multiple of 256 long), counts its output, reserves it with ONE atomic on the counter
-// (a few hundred arrivals instead of one per 256 items: same-address atomics serialise at the
-// memory side), then writes its items in order with a running offset.
-constexpr int TL_BLOCKS = 256;
-__device__ __forceinline__ int tl_block_excl(int v, int& total, int* wsum) {  // 256-thread exclusive scan
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    __syncthreads();  // (wsum reuse)
-    if (lane == 63) wsum[wid] = incl;
-    __syncthreads();
-    int pre = 0;
-    for (int w = 0; w < wid; w++) pre += wsum[w];
-    total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    return pre + incl - v;
-}
-// The valid slots of the iteration as a list of (alive, NS)-layout indices (ray n's first n_eff[n]
-// slots), count into ctrl[4].  The field evaluates x[idx[p]] for p < count and writes its outputs at
-// idx[p] (its `order` operand), so nothing is copied.
-__global__ __launch_bounds__(256) void test_index_kernel(const int32_t* __restrict__ n_eff, int32_t* __restrict__ ctrl,
-                                                         int32_t* __restrict__ idx) {
-    const int64_t A = ctrl[0];
-    const int NS = ctrl[1];
-    const int64_t per = ((A + TL_BLOCKS - 1) / TL_BLOCKS + 255) & ~(int64_t)255;
-    const int64_t lo = (int64_t)blockIdx.x * per, hi = min(A, lo + per);
-    if (lo >= hi) return;  // (uniform)
-    __shared__ int wsum[4];
-    __shared__ int base;
-    int cnt = 0;
-    for (int64_t i = lo + threadIdx.x; i < hi; i += 256) cnt += n_eff[i];
-    int total;
-    (void)tl_block_excl(cnt, total, wsum);
-    if (threadIdx.x == 0) base = total ? atomicAdd(ctrl + 4, total) : 0;
-    __syncthreads();
-    int run = base;
-    for (int64_t c0 = lo; c0 < hi; c0 += 256) {
-        const int64_t n = c0 + threadIdx.x;
-        const int c = n < hi ? n_eff[n] : 0;
-        int tot;
-        const int off = run + tl_block_excl(c, tot, wsum);
-        const int first = (int)(n * NS);
-        for (int s = 0; s < c; s++) idx[off + s] = first + s;
-        run += tot;
-    }
-}
-// After the compositor: the rays it kept (alive >= 0) compacted into alive_next (order irrelevant:
-// every ray is independent), their count into ctrl[5].
-__global__ __launch_bounds__(256) void test_alive_compact_kernel(const int64_t* __restrict__ alive,
-                                                                 int64_t* __restrict__ alive_next,
-                                                                 int32_t* __restrict__ ctrl) {
-    const int64_t A = ctrl[0];
-    const int64_t per = ((A + TL_BLOCKS - 1) / TL_BLOCKS + 255) & ~(int64_t)255;
-    const int64_t lo = (int64_t)blockIdx.x * per, hi = min(A, lo + per);
-    if (lo >= hi) return;  // (uniform)
-    __shared__ int wsum[4];
-    __shared__ int base;
-    int cnt = 0;
-    for (int64_t i = lo + threadIdx.x; i < hi; i += 256) cnt += alive[i] >= 0;
-    int total;
-    (void)tl_block_excl(cnt, total, wsum);
-    if (threadIdx.x == 0) base = total ? atomicAdd(ctrl + 5, total) : 0;
-    __syncthreads();
-    int run = base;
-    for (int64_t c0 = lo; c0 < hi; c0 += 256) {
-        const int64_t n = c0 + threadIdx.x;
-        const int64_t r = n < hi ? alive[n] : -1;
-        int tot;
-        const int off = run + tl_block_excl(r >= 0, tot, wsum);
-        if (r >= 0) alive_next[off] = r;
-        run += tot;
-    }
-}
-__global__ void test_loop_next_kernel(int32_t* __restrict__ ctrl, int64_t* __restrict__ total, int n_rays,
-                                      int max_samples, int min_samples) {
-    if (threadIdx.x != 0 || ctrl[3]) return;
-    total[0] += ctrl[4];
-    ctrl[6] += 1;
-    ctrl[7] += ctrl[0] * ctrl[1];
-    const int na = ctrl[5];
-    ctrl[4] = 0;
-    ctrl[5] = 0;
-    const int samples = ctrl[2];
-    if (na == 0 || samples >= max_samples) {
-        ctrl[3] = 1;
-        ctrl[0] = 0;
-        return;
-    }
-    const int ns = max(min(n_rays / na, 64), min_samples);
-    ctrl[0] = na;
-    ctrl[1] = ns;
-    ctrl[2] = samples + ns;
-}
-
-// ---------------------------------------------------------------------------------------------
-// raymarching.cu:62-70, 90-101, 122-141
-__global__ void morton3D_kernel(const int32_t* __restrict__ c, int64_t n, int32_t* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    out[i] = (int32_t)morton3D((uint32_t)c[3 * i], (uint32_t)c[3 * i + 1], (uint32_t)c[3 * i + 2]);
-}
-__global__ void morton3D_invert_kernel(const int32_t* __restrict__ idx, int64_t n, int32_t* __restrict__ c) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int32_t ind = idx[i];
-    c[3 * i + 0] = (int32_t)morton3D_invert((uint32_t)(ind >> 0));
-    c[3 * i + 1] = (int32_t)morton3D_invert((uint32_t)(ind >> 1));
-    c[3 * i + 2] = (int32_t)morton3D_invert((uint32_t)(ind >> 2));
-}
-// total_samples.sum() of VolumeRenderer.forward (custom_functions.py:139-146) in one workgroup,
-// optionally adding the marcher's count and that sum into a running f64 pair (throughput counters
-// that stay on the device: no per-step copies).
-__global__ __launch_bounds__(1024) void count_samples_kernel(const int64_t* __restrict__ total, int64_t R,
-                                                             const int32_t* __restrict__ counter,
-                                                             int64_t* __restrict__ sum_out, double* __restrict__ acc) {
-    count_samples_wg(total, R, counter, sum_out, acc);
-}
-
-__global__ void packbits_kernel(const float4* __restrict__ grid, int64_t n_bytes, float thr,
-                                uint8_t* __restrict__ bitfield) {
-    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (n >= n_bytes) return;
-    const float4 lo = grid[2 * n], hi = grid[2 * n + 1];
-    const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    uint32_t bits = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) bits |= (v[i] > thr) ? (1u << i) : 0u;
-    bitfield[n] = (uint8_t)bits;
-}
-
-// RayMarcher.backward (custom_functions.py:102-112): torch_scatter.segment_csr over
-// indptr = [rays_a[:, 1], rays_a[-1, 1] + rays_a[-1, 2]], so row r sums samples
-// [rays_a[r, 1], rays_a[r + 1, 1]) (the last row up to its start + count; an inverted range sums to 0):
-//   dL/drays_o[r] = sum dL/dxyzs,   dL/drays_d[r] = sum (dL/dxyzs * ts + dL/ddirs).
-// One wave per row, no atomics: lane l adds samples l, l + 64, ... in order, then the fixed
-// permlane/DPP tree of wave_sum_multi — the summation order depends only on the segment, so
-// repeated launches are bit-identical.  The d-term is rounded as the reference's torch ops round it
-// (a product, then a sum: no fma contraction).  gx / gd may be NULL (that gradient is zero).
-__global__ __launch_bounds__(256) void segment_csr_kernel(const float* __restrict__ gx, const float* __restrict__ gd,
-                                                          const float* __restrict__ ts,
-                                                          const int64_t* __restrict__ rays_a, int64_t R,
-                                                          float* __restrict__ d_o, float* __restrict__ d_d) {
-#pragma clang fp contract(off)
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= R) return;  // wave-uniform
-    const int lane = threadIdx.x & 63;
-    const int64_t start = rays_a[3 * r + 1];
-    const int64_t end = (r + 1 < R) ? rays_a[3 * (r + 1) + 1] : start + rays_a[3 * r + 2];
-    float a[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int64_t s = start + lane; s < end; s += 64) {
-        const float t = ts[s];
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const float x = gx ? gx[3 * s + c] : 0.f;
-            const float y = gd ? gd[3 * s + c] : 0.f;
-            a[c] = a[c] + x;
-            a[3 + c] = a[3 + c] + ((x * t) + y);
-        }
-    }
-    wave_sum_multi<6>(a);
-    if (lane < 3) {
-        const float vo = lane == 0 ? a[0] : (lane == 1 ? a[1] : a[2]);
-        const float vd = lane == 0 ? a[3] : (lane == 1 ? a[4] : a[5]);
-        d_o[3 * r + lane] = vo;
-        d_d[3 * r + lane] = vd;
-    }
-}
-
-}  // namespace ncn
+#include "vren_march.h"
+#include "vren_march_wave.h"
+#include "vren_march_pack.h"
+#include "vren_aabb.h"
+#include "vren_composite_fw.h"
+#include "vren_composite_bw.h"
+#include "vren_test_loop.h"
+#include "vren_util.h"
 
 using namespace ncn;
 
 // ------------------------------------------------------------------------------------------------
-// C ABI
+// Launch helpers, then the C ABI
+// Launches KERNEL<cascades == 1> (the marchers' ONE_CASCADE instance, or the general one) ...
+#define NCN_LAUNCH_CASCADES(CASCADES, KERNEL, ...)                          \
+    do {                                                                    \
+        if ((CASCADES) == 1) hipLaunchKernelGGL(KERNEL<true>, __VA_ARGS__); \
+        else hipLaunchKernelGGL(KERNEL<false>, __VA_ARGS__);                \
+    } while (0)
+// ... and KERNEL<cascades == 1, P> of the wave-parallel walk (P sub-windows per iteration).
+#define NCN_LAUNCH_CASCADES_P(CASCADES, KERNEL, P, ...)                          \
+    do {                                                                         \
+        if ((CASCADES) == 1) hipLaunchKernelGGL((KERNEL<true, P>), __VA_ARGS__); \
+        else hipLaunchKernelGGL((KERNEL<false, P>), __VA_ARGS__);                \
+    } while (0)
+
+// raymarching_test for ncn_march_test (ctrl NULL) and the device-driven loop (n_samples from ctrl).
+static void launch_march_test(const float* rays_o, const float* rays_d, float* hits_t, const int64_t* alive,
+                              int64_t n_alive, const uint8_t* bitfield, int cascades, float scale,
+                              float exp_step_factor, int grid_size, int max_samples, int n_samples, float* xyzs,
+                              float* dirs, float* deltas, float* ts, int32_t* n_eff, const int32_t* ctrl,
+                              hipStream_t s) {
+    NCN_LAUNCH_CASCADES(cascades, march_test_kernel, dim3(cdiv(n_alive, 64)), dim3(64), 0, s, rays_o, rays_d, hits_t,
+                        alive, n_alive, bitfield, cascades, scale, exp_step_factor, grid_size, max_samples, n_samples,
+                        xyzs, dirs, deltas, ts, n_eff, ctrl);
+}
+
+// composite_test_multi_fw for its three entries (offsets / ctrl NULL where the entry has none).
+static void launch_composite_test(const float* sigmas, const float* raws, const float* deltas, const float* ts,
+                                  int64_t* alive, int64_t n_alive, int n_samples, int n_rend, float T_threshold,
+                                  const int32_t* n_eff, float* opacity, float* depth, float* rend,
+                                  const int32_t* offsets, const int32_t* ctrl, hipStream_t s) {
+    hipLaunchKernelGGL(composite_test_kernel, dim3(cdiv(n_alive, 256)), dim3(256), 0, s, sigmas, raws, deltas, ts,
+                       alive, n_alive, n_samples, n_rend, T_threshold, n_eff, opacity, depth, rend, offsets, ctrl);
+}
+
 extern "C" {
 
 int ncn_morton3D(const int32_t* coords, int64_t n, int32_t* out, void* stream) {
@@ -1817,26 +146,16 @@ int ncn_march_train_walk(const float* rays_o, const float* rays_d, const float* 
                 "ncn_march_train_walk: bad cascades/grid_size/max_samples");
     if (exp_step_factor == 0.0f) {  // constant dt: the wave-parallel walk
         dim3 g(cdiv(n_rays, 4)), b(256);
-        if (cascades == 1)
-            hipLaunchKernelGGL((march_train_wave_kernel<true, 2>), g, b, 0, (hipStream_t)stream, rays_o, rays_d, hits_t,
-                               noise, n_rays, bitfield, cascades, scale, grid_size, max_samples, counts, slab_xyz,
-                               slab_t, slab_dt);
-        else
-            hipLaunchKernelGGL((march_train_wave_kernel<false, 2>), g, b, 0, (hipStream_t)stream, rays_o, rays_d,
-                               hits_t, noise, n_rays, bitfield, cascades, scale, grid_size, max_samples, counts,
-                               slab_xyz, slab_t, slab_dt);
+        NCN_LAUNCH_CASCADES_P(cascades, march_train_wave_kernel, 2, g, b, 0, (hipStream_t)stream, rays_o, rays_d,
+                              hits_t, noise, n_rays, bitfield, cascades, scale, grid_size, max_samples, counts,
+                              slab_xyz, slab_t, slab_dt);
         NCN_LAUNCH_CHECK("ncn_march_train_walk");
         return 0;
     }
     dim3 g(cdiv(n_rays, 64)), b(64);
-    if (cascades == 1)
-        hipLaunchKernelGGL(march_train_walk_kernel<true>, g, b, 0, (hipStream_t)stream, rays_o, rays_d, hits_t, noise,
-                           n_rays, bitfield, cascades, scale, exp_step_factor, grid_size, max_samples, counts,
-                           slab_xyz, slab_t, slab_dt);
-    else
-        hipLaunchKernelGGL(march_train_walk_kernel<false>, g, b, 0, (hipStream_t)stream, rays_o, rays_d, hits_t,
-                           noise, n_rays, bitfield, cascades, scale, exp_step_factor, grid_size, max_samples, counts,
-                           slab_xyz, slab_t, slab_dt);
+    NCN_LAUNCH_CASCADES(cascades, march_train_walk_kernel, g, b, 0, (hipStream_t)stream, rays_o, rays_d, hits_t,
+                        noise, n_rays, bitfield, cascades, scale, exp_step_factor, grid_size, max_samples, counts,
+                        slab_xyz, slab_t, slab_dt);
     NCN_LAUNCH_CHECK("ncn_march_train_walk");
     return 0;
 }
@@ -1860,14 +179,9 @@ int ncn_march_train_fused(const float* rays_o, const float* rays_d, int64_t n_ra
     int32_t* wg_sum = counts + n_rays;
     hipStream_t s = (hipStream_t)stream;
     dim3 g(nwg), b(256);
-#define NCN_WALK2_ARGS                                                                                         \
-    rays_o, rays_d, n_rays, cx, cy, cz, hx, hy, hz, near_distance, noise, seed, rng_counter, bitfield, cascades, \
-        scale, grid_size, max_samples, slab_xyz, slab_t, slab_dt, counts, wg_sum
-    if (cascades == 1)
-        hipLaunchKernelGGL((march_train_walk2_kernel<true, 2>), g, b, 0, s, NCN_WALK2_ARGS);
-    else
-        hipLaunchKernelGGL((march_train_walk2_kernel<false, 2>), g, b, 0, s, NCN_WALK2_ARGS);
-#undef NCN_WALK2_ARGS
+    NCN_LAUNCH_CASCADES_P(cascades, march_train_walk2_kernel, 2, g, b, 0, s, rays_o, rays_d, n_rays, cx, cy, cz, hx,
+                          hy, hz, near_distance, noise, seed, rng_counter, bitfield, cascades, scale, grid_size,
+                          max_samples, slab_xyz, slab_t, slab_dt, counts, wg_sum);
     NCN_LAUNCH_CHECK("ncn_march_train_fused(walk)");
     hipLaunchKernelGGL(march_train_place_kernel, g, b, 0, s, rays_d, n_rays, max_samples, counts, wg_sum, slab_xyz,
                        slab_t, slab_dt, rays_a, xyzs, dirs, deltas, ts, counter);
@@ -1898,15 +212,8 @@ int ncn_march_test(const float* rays_o, const float* rays_d, float* hits_t, cons
                    void* stream) {
     if (n_alive <= 0) return 0;
     NCN_REQUIRE(cascades >= 1 && grid_size >= 1 && n_samples >= 1, hipErrorInvalidValue, "ncn_march_test: bad args");
-    dim3 g(cdiv(n_alive, 64)), b(64);
-    if (cascades == 1)
-        hipLaunchKernelGGL(march_test_kernel<true>, g, b, 0, (hipStream_t)stream, rays_o, rays_d, hits_t, alive,
-                           n_alive, bitfield, cascades, scale, exp_step_factor, grid_size, max_samples, n_samples,
-                           xyzs, dirs, deltas, ts, n_eff, (const int32_t*)nullptr);
-    else
-        hipLaunchKernelGGL(march_test_kernel<false>, g, b, 0, (hipStream_t)stream, rays_o, rays_d, hits_t, alive,
-                           n_alive, bitfield, cascades, scale, exp_step_factor, grid_size, max_samples, n_samples,
-                           xyzs, dirs, deltas, ts, n_eff, (const int32_t*)nullptr);
+    launch_march_test(rays_o, rays_d, hits_t, alive, n_alive, bitfield, cascades, scale, exp_step_factor, grid_size,
+                      max_samples, n_samples, xyzs, dirs, deltas, ts, n_eff, nullptr, (hipStream_t)stream);
     NCN_LAUNCH_CHECK("ncn_march_test");
     return 0;
 }
@@ -1915,15 +222,19 @@ int ncn_march_test(const float* rays_o, const float* rays_d, float* hits_t, cons
 // the ones whose first row is short exit at once.
 static int cf_coop_blocks(int64_t n_rays) { return (int)std::min<int64_t>(n_rays, 256); }
 
+// KERNEL: a macro from the channel count to the kernel instance
 #define NCN_DISPATCH_C(C_RT, KERNEL, ...)                                                       \
     switch (C_RT) {                                                                            \
-        case 1: hipLaunchKernelGGL(KERNEL<1>, __VA_ARGS__); break;                             \
-        case 3: hipLaunchKernelGGL(KERNEL<3>, __VA_ARGS__); break;                             \
-        case 4: hipLaunchKernelGGL(KERNEL<4>, __VA_ARGS__); break;                             \
-        case 6: hipLaunchKernelGGL(KERNEL<6>, __VA_ARGS__); break;                             \
+        case 1: hipLaunchKernelGGL(KERNEL(1), __VA_ARGS__); break;                             \
+        case 3: hipLaunchKernelGGL(KERNEL(3), __VA_ARGS__); break;                             \
+        case 4: hipLaunchKernelGGL(KERNEL(4), __VA_ARGS__); break;                             \
+        case 6: hipLaunchKernelGGL(KERNEL(6), __VA_ARGS__); break;                             \
         default: ncn::set_error("unsupported n_rend=%d (supported: 1,3,4,6)", C_RT);           \
                  return (int)hipErrorInvalidValue;                                             \
     }
+#define NCN_FW_KERNEL(C) (composite_fw_kernel<C>)
+#define NCN_BW_KERNEL(C) (composite_bw_kernel<C, false>)
+#define NCN_BW_KERNEL_DWS(C) (composite_bw_kernel<C, true>)
 
 int ncn_composite_train_fw_bg(const float* sigmas, const float* raws, const float* deltas, const float* ts,
                               const int64_t* rays_a, int64_t n_rays, int64_t n_samples, int n_rend, float T_threshold,
@@ -1932,7 +243,7 @@ int ncn_composite_train_fw_bg(const float* sigmas, const float* raws, const floa
     if (n_rays <= 0) return 0;
     (void)n_samples;
     const int n_coop = cf_coop_blocks(n_rays);
-    NCN_DISPATCH_C(n_rend, composite_fw_kernel, dim3(n_coop + cdiv(n_rays, CF_WPB)), dim3(64 * CF_WPB), 0,
+    NCN_DISPATCH_C(n_rend, NCN_FW_KERNEL, dim3(n_coop + cdiv(n_rays, CF_WPB)), dim3(64 * CF_WPB), 0,
                    (hipStream_t)stream, sigmas, raws, deltas, ts, rays_a, n_rays, T_threshold, total_samples, opacity,
                    depth, rend, ws, bg, rgb_bg, n_coop);
     NCN_LAUNCH_CHECK("ncn_composite_train_fw");
@@ -1958,11 +269,11 @@ int ncn_composite_train_bw_bg(const float* dL_dopacity, const float* dL_ddepth, 
     const int n_coop = cf_coop_blocks(n_rays);
     const dim3 grid(n_coop + cdiv(n_rays, CF_WPB));
     if (dL_dws) {
-        NCN_DISPATCH_C(n_rend, composite_bw_kernel_dws, grid, dim3(64 * CF_WPB), 0, (hipStream_t)stream, dL_dopacity,
+        NCN_DISPATCH_C(n_rend, NCN_BW_KERNEL_DWS, grid, dim3(64 * CF_WPB), 0, (hipStream_t)stream, dL_dopacity,
                    dL_ddepth, dL_drgb, dL_dws, sigmas, raws, ws, deltas, ts, rays_a, n_rays, opacity, depth, rend,
                    T_threshold, dL_dsigmas, dL_draws, bg, n_coop);
     } else {
-        NCN_DISPATCH_C(n_rend, composite_bw_kernel_nodws, grid, dim3(64 * CF_WPB), 0, (hipStream_t)stream, dL_dopacity,
+        NCN_DISPATCH_C(n_rend, NCN_BW_KERNEL, grid, dim3(64 * CF_WPB), 0, (hipStream_t)stream, dL_dopacity,
                    dL_ddepth, dL_drgb, dL_dws, sigmas, raws, ws, deltas, ts, rays_a, n_rays, opacity, depth, rend,
                    T_threshold, dL_dsigmas, dL_draws, bg, n_coop);
     }
@@ -1984,9 +295,8 @@ int ncn_composite_test_fw(const float* sigmas, const float* raws, const float* d
                           int64_t* alive, int64_t n_alive, int n_samples, int n_rend, float T_threshold,
                           const int32_t* n_eff, float* opacity, float* depth, float* rend, void* stream) {
     if (n_alive <= 0) return 0;
-    hipLaunchKernelGGL(composite_test_kernel, dim3(cdiv(n_alive, 256)), dim3(256), 0, (hipStream_t)stream, sigmas,
-                       raws, deltas, ts, alive, n_alive, n_samples, n_rend, T_threshold, n_eff, opacity, depth, rend,
-                       (const int32_t*)nullptr, (const int32_t*)nullptr);
+    launch_composite_test(sigmas, raws, deltas, ts, alive, n_alive, n_samples, n_rend, T_threshold, n_eff, opacity,
+                          depth, rend, nullptr, nullptr, (hipStream_t)stream);
     NCN_LAUNCH_CHECK("ncn_composite_test_fw");
     return 0;
 }
@@ -2013,9 +323,8 @@ int ncn_composite_test_fw_compact(const float* sigmas_c, const float* raws_c, co
                                   float* depth, float* rend, void* stream) {
     if (n_alive <= 0) return 0;
     NCN_REQUIRE(offsets != nullptr, hipErrorInvalidValue, "ncn_composite_test_fw_compact: offsets required");
-    hipLaunchKernelGGL(composite_test_kernel, dim3(cdiv(n_alive, 256)), dim3(256), 0, (hipStream_t)stream, sigmas_c,
-                       raws_c, deltas, ts, alive, n_alive, n_samples, n_rend, T_threshold, n_eff, opacity, depth, rend,
-                       offsets, (const int32_t*)nullptr);
+    launch_composite_test(sigmas_c, raws_c, deltas, ts, alive, n_alive, n_samples, n_rend, T_threshold, n_eff, opacity,
+                          depth, rend, offsets, nullptr, (hipStream_t)stream);
     NCN_LAUNCH_CHECK("ncn_composite_test_fw_compact");
     return 0;
 }
@@ -2026,15 +335,8 @@ int ncn_test_loop_march(const float* rays_o, const float* rays_d, float* hits_t,
                         float* ts, int32_t* n_eff, void* stream) {
     if (max_alive <= 0) return 0;
     NCN_REQUIRE(cascades >= 1 && grid_size >= 1 && ctrl, hipErrorInvalidValue, "ncn_test_loop_march: bad args");
-    dim3 g(cdiv(max_alive, 64)), b(64);
-    if (cascades == 1)
-        hipLaunchKernelGGL(march_test_kernel<true>, g, b, 0, (hipStream_t)stream, rays_o, rays_d, hits_t, alive,
-                           max_alive, bitfield, cascades, scale, exp_step_factor, grid_size, max_samples, 1, xyzs,
-                           dirs, deltas, ts, n_eff, ctrl);
-    else
-        hipLaunchKernelGGL(march_test_kernel<false>, g, b, 0, (hipStream_t)stream, rays_o, rays_d, hits_t, alive,
-                           max_alive, bitfield, cascades, scale, exp_step_factor, grid_size, max_samples, 1, xyzs,
-                           dirs, deltas, ts, n_eff, ctrl);
+    launch_march_test(rays_o, rays_d, hits_t, alive, max_alive, bitfield, cascades, scale, exp_step_factor, grid_size,
+                      max_samples, 1, xyzs, dirs, deltas, ts, n_eff, ctrl, (hipStream_t)stream);
     NCN_LAUNCH_CHECK("ncn_test_loop_march");
     return 0;
 }
@@ -2051,9 +353,8 @@ int ncn_test_loop_composite(const float* sigmas_c, const float* raws_c, const in
                             float T_threshold, const int32_t* n_eff, float* opacity, float* depth, float* rend,
                             void* stream) {
     if (max_alive <= 0) return 0;
-    hipLaunchKernelGGL(composite_test_kernel, dim3(cdiv(max_alive, 256)), dim3(256), 0, (hipStream_t)stream, sigmas_c,
-                       raws_c, deltas, ts, alive, max_alive, 1, n_rend, T_threshold, n_eff, opacity, depth, rend,
-                       offsets, ctrl);
+    launch_composite_test(sigmas_c, raws_c, deltas, ts, alive, max_alive, 1, n_rend, T_threshold, n_eff, opacity,
+                          depth, rend, offsets, ctrl, (hipStream_t)stream);
     NCN_LAUNCH_CHECK("ncn_test_loop_composite");
     return 0;
 }

@@ -94,7 +94,7 @@ def test_raymarching_train_bitexact(dev, scene, n, edge, ms):
 
 
 def _march_uniform_np(seed, ctr, n):
-    """numpy restatement of march_uniform (csrc/vren.hip): splitmix64 of (seed, counter, ray)."""
+    """numpy restatement of march_uniform (csrc/vren_march_wave.h): splitmix64 of (seed, counter, ray)."""
     M = (1 << 64) - 1
     out = np.empty(n, np.float32)
     for r in range(n):
@@ -294,6 +294,78 @@ def test_composite_long_rays_workgroup_path(dev, extra_long):
         r2 = vren_ref.composite_train_multi_bw(dO, dD, dR, dW, sig, raws, ws, deltas, ts, rays_a, O, D, RE, 1e-4)
         for a, r, name in zip(o2, r2, ("dL_dsigmas", "dL_draws")):
             np.testing.assert_allclose(a.cpu().numpy(), r, rtol=1e-3, atol=1e-4 * np.abs(r).max(), err_msg=name)
+
+
+N_COOP = 256  # the compositors' workgroups for long rows at the front of the grid (cf_coop_blocks)
+
+
+def _channel_inputs(C):
+    """One segment of every length at which the compositors change path (row blocks of 1/2/4, the
+    256-sample threshold of the workgroup path, its 1024-sample cap and beyond; 1024 twice), sigma as
+    in _long_first_inputs: |N(0, 0.2)| keeps T well above 1e-4, so a ray stops only at a 1e5 sample.
+    About half of the segments hold one; among the rays the workgroup path takes (257..1024 samples)
+    the stops fall in each of its four waves (samples 100, 300, 600, 900) and the 512-sample ray has
+    none.  In front of them, in ray order, N_COOP rays of 1 or 0 samples: in ray order every long
+    row then has a short row N_COOP rows ahead of it, so no workgroup takes it (cf_coop_takes) and it
+    composites on the single-wave path; with the long rows first the workgroups take them."""
+    lens = [1, 0] * (N_COOP // 2) + [0, 1, 63, 64, 65, 128, 129, 256, 257, 511, 512, 1024, 1024, 1025, 1300]
+    stops = [None] * N_COOP + [None, None, None, None, 40, None, 100, None, 100, 300, None, 600, 900, 600, 1100]
+    rng = np.random.default_rng(10 + C)
+    rows, start, sig_parts = [], 0, []
+    for i, (n, stop) in enumerate(zip(lens, stops)):
+        rows.append([i, start, n])
+        s = np.abs(rng.normal(0, 0.2, n)).astype(np.float32)
+        if stop is not None:
+            s[stop] = 1e5
+        sig_parts.append(s)
+        start += n
+    by_ray = np.array(rows, np.int64)
+    long_rows = np.nonzero(by_ray[:, 2] > 256)[0]
+    assert (long_rows >= N_COOP).all() and (by_ray[long_rows - N_COOP, 2] <= 256).all()  # ray order: single-wave
+    order = rng.permutation(len(rows))
+    long_first = by_ray[np.concatenate([order[by_ray[order, 2] > 256], order[by_ray[order, 2] <= 256]])]
+    S = start
+    sig = np.concatenate(sig_parts)
+    raws = rng.random((S, C), dtype=np.float32)
+    deltas = np.full(S, 1.7e-3, np.float32)
+    ts = (np.arange(S) % 977 * 1.7e-3).astype(np.float32)
+    return long_first, by_ray, deltas, ts, sig, raws
+
+
+@pytest.mark.parametrize("C", [1, 4, 6])
+def test_composite_channels_every_path(dev, C):
+    """The compositors at C != 3 (the per-channel scan branch of the backward) over every segment
+    length at which they change path, rows long-first (the step's order: the 257..1024-sample rays on
+    the workgroup path) and in ray order (the same rays on the single-wave path, see _channel_inputs):
+    forward exact counts and 2e-4 values against the oracle, the two row orders, i.e. the two paths,
+    bit-identical; backward on either path without / with dL_dws and with the background folded in
+    (bg = 0.7: the oracle with dL_dopacity - bg * sum_i dL_drgb_i) at the parity tolerance."""
+    long_first, by_ray, deltas, ts, sig, raws = _channel_inputs(C)
+    T = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    ref = vren_ref.composite_train_multi_fw(sig, raws, deltas, ts, by_ray, 1e-4)  # indexed by ray: any row order
+    outs = []
+    for rays_a in (long_first, by_ray):
+        out = vren.composite_train_multi_fw(T(sig), T(raws), T(deltas), T(ts), T(rays_a), 1e-4)
+        assert np.array_equal(out[0].cpu().numpy(), ref[0])
+        for a, r, name in zip(out[1:], ref[1:], ("opacity", "depth", "rend", "ws")):
+            np.testing.assert_allclose(a.cpu().numpy(), r, rtol=2e-4, atol=2e-5, err_msg=name)
+        outs.append(out)
+    for a, b_ in zip(*outs):
+        assert torch.equal(a, b_)
+    _, O, D, RE, ws = ref
+    rng = np.random.default_rng(4)
+    R, S = by_ray.shape[0], sig.shape[0]
+    dO, dD = rng.normal(size=R).astype(np.float32), rng.normal(size=R).astype(np.float32)
+    dR = rng.normal(size=(R, C)).astype(np.float32)
+    dW = rng.normal(size=S).astype(np.float32)
+    for dW_, bg in ((None, None), (dW, None), (None, 0.7)):
+        dO_ref = dO if bg is None else (dO - np.float32(bg) * dR.sum(1, dtype=np.float32)).astype(np.float32)
+        r2 = vren_ref.composite_train_multi_bw(dO_ref, dD, dR, dW_, sig, raws, ws, deltas, ts, by_ray, O, D, RE, 1e-4)
+        for rays_a in (long_first, by_ray):
+            o2 = vren.composite_train_multi_bw(T(dO), T(dD), T(dR), T(dW_), T(sig), T(raws), T(ws), T(deltas), T(ts),
+                                               T(rays_a), T(O), T(D), T(RE), 1e-4, bg=bg)
+            for a, r, name in zip(o2, r2, ("dL_dsigmas", "dL_draws")):
+                np.testing.assert_allclose(a.cpu().numpy(), r, rtol=1e-3, atol=1e-4 * np.abs(r).max(), err_msg=name)
 
 
 @pytest.mark.parametrize("with_dws", [False, True])

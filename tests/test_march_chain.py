@@ -1,4 +1,4 @@
-"""CPU check of the closed-form chain behind the wave-parallel marcher (csrc/vren.hip march_chain).
+"""CPU check of the closed-form chain behind the wave-parallel marcher (csrc/vren_march_wave.h march_chain).
 
 The reference walk advances t by repeated float32 adds c_{k+1} = fl(c_k + dt) (raymarching.cu:221-233).
 march_chain computes a window of that chain in closed form (constant bit-pattern step inside a binade,

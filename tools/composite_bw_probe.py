@@ -1,7 +1,7 @@
 """Diagnostic: time the training composite backward (ncn_composite_train_bw_bg without dL_dws, the
 step's form) on a marched bench batch for the main library and tools/_build/vren_*.so variants
-(csrc/vren.hip built with -D knobs), and check bit-identity of dL/dsigma and dL/draws against the
-main library.  Not part of the product."""
+(csrc/vren.hip, whose compositors are csrc/vren_composite*.h, built with -D knobs), and check
+bit-identity of dL/dsigma and dL/draws against the main library.  Not part of the product."""
 import ctypes
 import glob
 import os

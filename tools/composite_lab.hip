@@ -1,6 +1,6 @@
 // Diagnostic lab (not product code): variants of the train composite forward on the same inputs,
 // timed by tools/composite_lab.py.  Every variant has the signature of ncn_composite_train_fw
-// plus a variant id; the product kernel lives in normal-clustering-nerf_amd/csrc/vren.hip.
+// plus a variant id; the product kernel lives in normal-clustering-nerf_amd/csrc/vren_composite_fw.h.
 #include "../normal-clustering-nerf_amd/csrc/common.h"
 
 using namespace ncn;

@@ -1,4 +1,4 @@
-// Diagnostic lab (not product code): the product composite forward (csrc/vren.hip) with switches
+// Diagnostic lab (not product code): the product composite forward (csrc/vren_composite_fw.h) with switches
 // that remove one piece of its dependency chain at a time, to attribute the kernel's time.
 // F_NOWS: no ws stores; F_ONEROUND: stop after the first round of ROWS rows (wrong for long rays);
 // F_FAKESEG: segment = (n * 70, 70) without waiting for rays_a (wrong, timing only).
