@@ -378,14 +378,10 @@ int ncn_field_scatter_wgrad(const float* xyzs, int64_t n, const int32_t* n_dev, 
 /* ---- normal clustering loss path: replaces _extract_normals_from_ray_batch
  *      (hypersim_src/utils.py:504-541) and the faiss + torch cluster block of NeRFMTLoss
  *      (losses.py:47-166, 420-478). ---- */
-/* ncn_photo_loss_fwd + ncn_normals_fwd in one launch (the fused loss node's independent parts). */
-int ncn_photo_normals_fwd(const float* rgb, const float* rgb_gt, const float* opacity, int64_t n_rays,
-                          float w_opacity, float* loss, const float* rays_o, const float* rays_d, const float* depth,
-                          const int64_t* x1, const int64_t* x2, const int64_t* x3, int64_t n_tri, float* normals,
-                          void* stream);
-/* The same plus the render's composited-sample count (ncn_count_samples: *count_out =
+/* ncn_photo_loss_fwd + ncn_normals_fwd in one launch (the fused loss node's independent parts),
+ * plus the render's composited-sample count (ncn_count_samples: *count_out =
  * sum(total_samples[0..n_count)), count_acc += {counter[0], the sum} when non-NULL) in one extra
- * workgroup of the launch; total_samples NULL = ncn_photo_normals_fwd. */
+ * workgroup of the launch; total_samples NULL = no count. */
 int ncn_photo_normals_count_fwd(const float* rgb, const float* rgb_gt, const float* opacity, int64_t n_rays,
                                 float w_opacity, float* loss, const float* rays_o, const float* rays_d,
                                 const float* depth, const int64_t* x1, const int64_t* x2, const int64_t* x3,
@@ -464,6 +460,33 @@ int ncn_cluster_loss(const float* normals, int64_t n_tri, int K, int niter, cons
                      float w_ort, float w_dot, float w_l1, const float* w_dev, const int64_t* step_dev,
                      float sched_start, float sched_grow, const float* photo_loss, float* out_losses,
                      int32_t* out_labels, float* out_centroids, float* dL_dnormals, float* workspace, void* stream);
+/* The split training step's loss node in two launches on `stream`, with no second queue:
+ * 1. ncn_photo_normals_count_fwd (n_count = n_rays) and, in more workgroups of the same launch,
+ *    dL_draws (n, 3) = what ncn_nerf_loss_bwd (up_total, up_terms NULL, its dL_drgb) followed by
+ *    ncn_composite_train_bw_bg (3 channels, dL_ddepth and dL_dws NULL) writes, bit for bit when the
+ *    photometric term is finite (photo_loss[2] = 1); the flag is not applied to dL_draws (it is
+ *    written by this same launch) but by launch 2, which takes zeros for it when the flag is 0.
+ * 2. ncn_cluster_loss (photo_loss given) and ncn_field_bwd_mlp_part part 1 (the rgb pass, dL_drgbs =
+ *    dL_draws, n_blocks as there: 0 = the pass's own grid) as two roles of ONE launch: workgroups
+ *    [0, 16) are the clustering, the others the rgb pass.  Every output of the two is bit for bit the
+ *    separate entry points'.  A workgroup of this launch takes a CU, so 16 + the rgb pass's
+ *    workgroups must not exceed the device's CUs x the kernel's workgroups per CU: checked before
+ *    anything is launched (hipErrorCooperativeLaunchTooLarge), for n_blocks as given even when fewer
+ *    workgroups would run, and before the n_rays <= 0 return, so a call with n_rays = 0 is that check
+ *    alone (the split step makes it before it is captured).  K in {10, 20}; n = 0: no rgb pass. */
+int ncn_split_loss_fused(const float* rgb, const float* rgb_gt, const float* opacity, int64_t n_rays, float w_opacity,
+                         float* photo_loss, const float* rays_o, const float* rays_d, const float* depth,
+                         const int64_t* x1, const int64_t* x2, const int64_t* x3, int64_t n_tri, float* normals,
+                         const int64_t* total_samples, const int32_t* counter, int64_t* count_out, double* count_acc,
+                         const float* up_total, const float* sigmas, const float* deltas, const int64_t* rays_a,
+                         float T_threshold, float* dL_draws, int K, int niter, const uint32_t* kmeans_plan,
+                         float t_similar, float w_ort, float w_dot, float w_l1, const float* w_dev,
+                         const int64_t* step_dev, float sched_start, float sched_grow, float* out_losses,
+                         int32_t* out_labels, float* out_centroids, float* dL_dnormals, float* workspace,
+                         const float* xyzs, const float* dirs, int64_t n, const int32_t* n_dev, const int32_t* order,
+                         const uint16_t* weights_packed, int precision, const uint16_t* enc_cache,
+                         const float* loss_scale, int n_blocks, float* slab, float* dE_ws, float* level_max,
+                         float* dh_stash, void* stream);
 /* Backward of the whole NeRFMTLoss in the reference configuration (photometric + opacity +
  * normal-clustering terms, `all_images_triang_patch` 8x8 patches: n_rays a multiple of 64, the
  * triangles of losses.py:307-313 in patch order, dL_dnormals the (3, 49*n_rays/64, 3) output of

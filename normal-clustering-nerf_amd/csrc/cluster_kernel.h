@@ -33,6 +33,7 @@ struct ClusterLds {
     unsigned char pmem[KM_CHUNK_MAX];  // training-set membership of the chunk's points (faiss subsampling)
     int total;
     int timed_out;  // the sticky status word, read once after the last grid barrier
+    int late_drop;  // km_grid_exit's word
     KmUpdLds<K> upd;
     SelLds<K> sel;
     ClStats S;
@@ -43,7 +44,7 @@ struct ClusterLds {
 #ifdef NCN_DIAG_CL_TIMES
 __device__ unsigned long long ncn_cl_times[64];
 #define CL_STAMP(i) \
-    if (blockIdx.x == 0 && threadIdx.x == 0 && (i) < 64) ncn_cl_times[(i)] = __builtin_amdgcn_s_memrealtime()
+    if (bid == 0 && threadIdx.x == 0 && (i) < 64) ncn_cl_times[(i)] = __builtin_amdgcn_s_memrealtime()
 #else
 #define CL_STAMP(i)
 #endif
@@ -52,19 +53,19 @@ __device__ unsigned long long ncn_cl_times[64];
 // every word of both buffers): both when nothing is clustered, the odd one when no round follows
 // round 0.
 template <int K>
-__device__ __forceinline__ void cl_void_tags(const KmWs& ws, unsigned seq, bool clustered) {
+__device__ __forceinline__ void cl_void_tags(const KmWs& ws, int bid, unsigned seq, bool clustered) {
     const long long vw = km_tagged(km_round_tag(seq, KM_VOID_ROUND), 0);
     for (int q = threadIdx.x; q < K * 4; q += KM_THREADS) {
-        if (!clustered) st_c(ws.part + blockIdx.x * K * 4 + q, vw);         // buffer 0
-        st_c(ws.part + (KM_BLOCKS + blockIdx.x) * K * 4 + q, vw);  // buffer 1
+        if (!clustered) st_c(ws.part + bid * K * 4 + q, vw);         // buffer 0
+        st_c(ws.part + (KM_BLOCKS + bid) * K * 4 + q, vw);  // buffer 1
     }
 }
 
 // ---- select: final cluster sizes = count column of the final-search partials; cluster selection;
 // label, flip sign and selected cluster per point; flipped member sums to p2 ----
 template <int K>
-__device__ __forceinline__ void cl_select_flip(ClusterLds<K>& L, const KmWs& ws, unsigned seq, int len, int niter_eff,
-                                               float t_sim) {
+__device__ __forceinline__ void cl_select_flip(ClusterLds<K>& L, const KmWs& ws, int bid, unsigned seq, int len,
+                                               int niter_eff, float t_sim) {
     const int tid = threadIdx.x;
     if (tid < K)
         L.cnt[tid] = sum_rows_tagged(ws.part + (niter_eff & 1) * KM_BLOCKS * K * 4, K * 4, 4 * tid + 3,
@@ -92,13 +93,13 @@ __device__ __forceinline__ void cl_select_flip(ClusterLds<K>& L, const KmWs& ws,
         atomicAdd(&L.acc[4 * c + 3], (unsigned long long)KM_FX);
     }
     __syncthreads();
-    if (tid < 12) st_c(ws.p2 + blockIdx.x * KM_P2_ROW + tid, (long long)L.acc[tid]);
+    if (tid < 12) st_c(ws.p2 + bid * KM_P2_ROW + tid, (long long)L.acc[tid]);
 }
 
 // ---- sums: the selected clusters' statistics from p2, then per-cluster partials of x.c, |x-c|_1,
 // sign(x-c) to p3 ----
 template <int K>
-__device__ __forceinline__ void cl_sums(ClusterLds<K>& L, const KmWs& ws, int len) {
+__device__ __forceinline__ void cl_sums(ClusterLds<K>& L, const KmWs& ws, int bid, int len) {
     const int tid = threadIdx.x;
     CL_STAMP(59);
     cluster_stats(ws, L.S);
@@ -120,14 +121,14 @@ __device__ __forceinline__ void cl_sums(ClusterLds<K>& L, const KmWs& ws, int le
             }
         }
         __syncthreads();
-        if (tid < 15) st_c(ws.p3 + blockIdx.x * KM_P3_ROW + tid, (long long)L.acc[tid]);
+        if (tid < 15) st_c(ws.p3 + bid * KM_P3_ROW + tid, (long long)L.acc[tid]);
     }
 }
 
 // ---- grad: the three cluster losses and their analytic gradient per point (losses.py:469-478),
 // labels, the weight schedule of losses.py:217 and the loss total ----
 template <int K>
-__device__ __forceinline__ void cl_grad(ClusterLds<K>& L, const KmWs& ws, bool clustered, int nv, int len, int64_t T3,
+__device__ __forceinline__ void cl_grad(ClusterLds<K>& L, const KmWs& ws, int bid, bool clustered, int nv, int len, int64_t T3,
                                         float w_ort, float w_dot, float w_l1, const float* __restrict__ w_dev,
                                         const int64_t* __restrict__ step_dev, float sched_start, float sched_grow,
                                         const float* __restrict__ photo, float* __restrict__ out_losses,
@@ -152,7 +153,7 @@ __device__ __forceinline__ void cl_grad(ClusterLds<K>& L, const KmWs& ws, bool c
         L.timed_out = (int)__hip_atomic_load(&ws.sync[KM_SYNC_STATUS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
     const bool ok = clustered && L.S.ok && L.timed_out == 0;
-    if (blockIdx.x == 0 && tid < K * 3) out_centroids[tid] = clustered ? (&L.C[0][0])[tid] : 0.f;
+    if (bid == 0 && tid < K * 3) out_centroids[tid] = clustered ? (&L.C[0][0])[tid] : 0.f;
     if (tid == 0) {
         float ort = 0.f, cdot = 0.f, cl1 = 0.f;
         if (ok) {
@@ -189,7 +190,7 @@ __device__ __forceinline__ void cl_grad(ClusterLds<K>& L, const KmWs& ws, bool c
                         L.G[tm][c][q] = (L.G[tm][c][q] - cc[c][q] * cg) / (fmaxf(L.S.cmn[c], 1e-12f) * L.S.cnt[c]);
                 }
         }
-        if (blockIdx.x == 0) {
+        if (bid == 0) {
             out_losses[0] = ort; out_losses[1] = cdot; out_losses[2] = cl1; out_losses[3] = (float)nv;
             out_losses[4] = w_ort * ort; out_losses[5] = w_dot * cdot; out_losses[6] = w_l1 * cl1;
             out_losses[7] = w_ort; out_losses[8] = w_dot; out_losses[9] = w_l1;
@@ -243,14 +244,16 @@ __device__ __forceinline__ void cl_grad(ClusterLds<K>& L, const KmWs& ws, bool c
 //               labels (-9 invalid), the weight schedule of losses.py:217 and the loss total
 // Every workgroup reduces the same partials in the same fixed order, so all of them hold
 // bit-identical centroids/statistics and the result is run-to-run deterministic.
+// The body is a device function of the workgroup's index bid in [0, KM_BLOCKS) and its LDS, so that
+// it can also run as one role of a wider launch (split_fused.hip); cluster_kernel below is the
+// launch of its own.  All of the workgroup's LDS is L: nothing here declares __shared__ storage.
 template <int K>
-__global__ __launch_bounds__(KM_THREADS) void cluster_kernel(
-    const float* __restrict__ normals, int n_tri, int niter, const uint32_t* __restrict__ plan_words, float t_sim,
-    float w_ort, float w_dot,
-    float w_l1, const float* __restrict__ w_dev, const int64_t* __restrict__ step_dev, float sched_start,
-    float sched_grow, const float* __restrict__ photo, float* __restrict__ wsb, float* __restrict__ out_losses,
+__device__ __forceinline__ void cluster_body(
+    ClusterLds<K>& L, const int bid, const float* __restrict__ normals, int n_tri, int niter,
+    const uint32_t* __restrict__ plan_words, float t_sim, float w_ort, float w_dot, float w_l1,
+    const float* __restrict__ w_dev, const int64_t* __restrict__ step_dev, float sched_start, float sched_grow,
+    const float* __restrict__ photo, float* __restrict__ wsb, float* __restrict__ out_losses,
     int32_t* __restrict__ out_labels, float* __restrict__ out_centroids, float* __restrict__ dn) {
-    __shared__ ClusterLds<K> L;
     const KmWs ws = km_ws(wsb, K);
     constexpr int NW = KM_THREADS / 64;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -304,7 +307,7 @@ __global__ __launch_bounds__(KM_THREADS) void cluster_kernel(
     const int nv = L.total;
     const bool clustered = nv >= K;
     int m0, len;
-    km_chunk(nv, m0, len);
+    km_chunk(bid, nv, m0, len);
     KmPlan plan;
     plan.p = plan_words;
     const bool plan_ok = plan.n_tri() == n_tri && plan.K() == K;
@@ -349,7 +352,7 @@ __global__ __launch_bounds__(KM_THREADS) void cluster_kernel(
         const int rhi = r + 1 < R ? __builtin_amdgcn_readlane(wo_lane, r + 1) : nv;
         // the (sorted) picks inside [rlo, rhi): k in [kbeg, kend)
         const int kbeg = (int)__popcll(__ballot(pk_lane < rlo)), kend = (int)__popcll(__ballot(pk_lane < rhi));
-        if (!(rlo < m0 + len && rhi > m0) && r % KM_BLOCKS != (int)blockIdx.x && kbeg == kend) return;
+        if (!(rlo < m0 + len && rhi > m0) && r % KM_BLOCKS != bid && kbeg == kend) return;
         const bool v = (flags >> r) & 1u;
         const int rank = L.woff[r][wid] + __popcll(__ballot(v) & lt);
         if (v) {
@@ -369,7 +372,7 @@ __global__ __launch_bounds__(KM_THREADS) void cluster_kernel(
                         for (int q = 0; q < 3; q++) L.pickv[L.pick_ord[k]][q] = ar[q];
                     }
                 }
-        } else if (r * KM_THREADS + tid < n_tri && r % KM_BLOCKS == (int)blockIdx.x) {  // invalid: label -9, zero grad
+        } else if (r * KM_THREADS + tid < n_tri && r % KM_BLOCKS == bid) {  // invalid: label -9, zero grad
             const int i = r * KM_THREADS + tid;
             out_labels[i] = -9;
 #pragma unroll
@@ -405,7 +408,7 @@ __global__ __launch_bounds__(KM_THREADS) void cluster_kernel(
     CL_STAMP(1);
     unsigned phase = 0;
     const unsigned seq = __hip_atomic_load(&ws.sync[KM_SYNC_SEQ], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (!clustered || niter_eff == 0) cl_void_tags<K>(ws, seq, clustered);
+    if (!clustered || niter_eff == 0) cl_void_tags<K>(ws, bid, seq, clustered);
     if (clustered) {
         // ---- niter + 1 Lloyd rounds (hand-off: tagged words, no grid barrier; the loop stays in the kernel:
         // as a function it costs cluster_kernel<10> a register) ----
@@ -440,26 +443,26 @@ __global__ __launch_bounds__(KM_THREADS) void cluster_kernel(
                 unsigned long long sum = 0ull;
 #pragma unroll
                 for (int c = 0; c < KM_ACC_COPIES; c++) sum += L.accr[c][tid];
-                st_c(ws.part + (it & 1) * KM_BLOCKS * K * 4 + blockIdx.x * K * 4 + tid,
+                st_c(ws.part + (it & 1) * KM_BLOCKS * K * 4 + bid * K * 4 + tid,
                      km_tagged(km_round_tag(seq, it), (long long)sum));
             }
             CL_STAMP(3 + 2 * it);
         }
-        cl_select_flip<K>(L, ws, seq, len, niter_eff, t_sim);
+        cl_select_flip<K>(L, ws, bid, seq, len, niter_eff, t_sim);
         km_grid_sync(ws.sync, ++phase);
-        cl_sums<K>(L, ws, len);
+        cl_sums<K>(L, ws, bid, len);
         km_grid_sync(ws.sync, ++phase);  // uniform: S.ok is the same in every workgroup
         CL_STAMP(62);
         if (L.S.ok) sum_partials(ws.p3, KM_P3_ROW, 15, L.st3);
         __syncthreads();
         CL_STAMP(63);
     }
-    cl_grad<K>(L, ws, clustered, nv, len, T3, w_ort, w_dot, w_l1, w_dev, step_dev, sched_start, sched_grow, photo, out_losses,
+    cl_grad<K>(L, ws, bid, clustered, nv, len, T3, w_ort, w_dot, w_l1, w_dev, step_dev, sched_start, sched_grow, photo, out_losses,
                out_labels, out_centroids, dn);
     // every launch (clustered or not) advances the tag sequence; the last workgroup out re-reads the
     // status word and, when it is set, drops the cluster terms of the WHOLE launch (a workgroup that
     // read the word before a late timeout set it has applied its gradient rows: they are zeroed here)
-    if (km_grid_exit(ws.sync)) {
+    if (km_grid_exit(ws.sync, L.late_drop)) {
         for (int64_t i = tid; i < 3 * T3; i += KM_THREADS) dn[i] = 0.f;
         if (tid == 0) {
             out_losses[0] = out_losses[1] = out_losses[2] = 0.f;
@@ -467,6 +470,18 @@ __global__ __launch_bounds__(KM_THREADS) void cluster_kernel(
             if (photo) out_losses[10] = photo[0] + photo[1];
         }
     }
+}
+
+template <int K>
+__global__ __launch_bounds__(KM_THREADS) void cluster_kernel(
+    const float* __restrict__ normals, int n_tri, int niter, const uint32_t* __restrict__ plan_words, float t_sim,
+    float w_ort, float w_dot,
+    float w_l1, const float* __restrict__ w_dev, const int64_t* __restrict__ step_dev, float sched_start,
+    float sched_grow, const float* __restrict__ photo, float* __restrict__ wsb, float* __restrict__ out_losses,
+    int32_t* __restrict__ out_labels, float* __restrict__ out_centroids, float* __restrict__ dn) {
+    __shared__ ClusterLds<K> L;
+    cluster_body<K>(L, (int)blockIdx.x, normals, n_tri, niter, plan_words, t_sim, w_ort, w_dot, w_l1, w_dev, step_dev,
+                    sched_start, sched_grow, photo, wsb, out_losses, out_labels, out_centroids, dn);
 }
 
 }  // namespace ncn

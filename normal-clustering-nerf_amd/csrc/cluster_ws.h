@@ -112,9 +112,8 @@ __device__ __forceinline__ void km_grid_sync(unsigned* sync, unsigned phase) {
 // the LAST departing workgroup only) whether the status word is set: every workgroup's output
 // stores are drained (vmcnt(0)) before its departure, so that workgroup can still overwrite the
 // whole launch's outputs — the drop decision is then uniform even when a workgroup timed out after
-// another one had read the word.
-__device__ __forceinline__ bool km_grid_exit(unsigned* sync) {
-    __shared__ int late_drop;
+// another one had read the word.  late_drop: one LDS word of the workgroup (ClusterLds).
+__device__ __forceinline__ bool km_grid_exit(unsigned* sync, int& late_drop) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -131,10 +130,10 @@ __device__ __forceinline__ bool km_grid_exit(unsigned* sync) {
     return late_drop != 0;
 }
 
-// This workgroup's contiguous chunk of the compacted points.
-__device__ __forceinline__ void km_chunk(int nv, int& m0, int& len) {
+// Workgroup bid's contiguous chunk of the compacted points.
+__device__ __forceinline__ void km_chunk(int bid, int nv, int& m0, int& len) {
     const int chunk = (nv + KM_BLOCKS - 1) / KM_BLOCKS;
-    m0 = blockIdx.x * chunk;
+    m0 = bid * chunk;
     len = max(0, min(nv, m0 + chunk) - m0);
 }
 

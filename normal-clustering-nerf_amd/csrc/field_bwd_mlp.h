@@ -397,18 +397,34 @@ __host__ __device__ inline int bwd_blocks_of(int64_t n) {
     return (int)(b < 1 ? 1 : (b > 256 ? 256 : b));
 }
 
-// (the sigma pass runs two workgroups per CU: 4 waves per SIMD, so at most 128 VGPRs)
+// The workgroup's LDS: the sigma pass keeps only the sigma_net fragments and its 11 exchange tiles
+// per group (57 KB: two workgroups per CU); the others all 34 + 8 fragments and 30 tiles (158 KB).
+template <typename T, int PART>
+struct BwdLds {
+    static constexpr bool SIGONLY = PART == BWD_SIGMA;
+    static constexpr int NF32 = SIGONLY ? N_SIG32 : N_FRAG32, NF16 = SIGONLY ? N_SIG16 : N_FRAG16, NX = x_count<PART>();
+    typename Mfma<T>::v8 F32s[NF32 * 64];
+    typename Mfma<T>::v4 F16s[NF16 * 64];
+    __attribute__((aligned(16))) uint16_t X[BWD_WAVES * NX * 256];  // dW operand images
+};
+
+// The pass as a device function of the workgroup's index bid in [0, nblk) and its LDS (the three
+// arrays of BwdLds), so that it can also run as one role of a wider launch (split_fused.hip);
+// field_bwd_kernel below is the launch of its own.  rgb_on (BWD_RGB): NULL, or a device flag whose
+// zero makes the pass take dL_drgb as zeros.
 template <typename T, int PART = BWD_ALL, bool DIN = false>
-__global__ __launch_bounds__(BWD_THREADS, PART == BWD_SIGMA ? 4 : 2) void field_bwd_kernel(
+__device__ __forceinline__ void field_bwd_body(
+    typename Mfma<T>::v8* __restrict__ const F32s, typename Mfma<T>::v4* __restrict__ const F16s,
+    uint16_t* __restrict__ const X, const int bid, const int nblk, const float* __restrict__ rgb_on,
     const float* __restrict__ dirs, int64_t n, const int32_t* __restrict__ n_dev, const uint16_t* __restrict__ wpacked,
     const typename Mfma<T>::v8* __restrict__ enc_cache, const float* __restrict__ dL_dsig,
     const float* __restrict__ dL_drgb, const float* __restrict__ loss_scale, float* __restrict__ dE_out,
     float* __restrict__ slab, float* __restrict__ level_max, const int32_t* __restrict__ order,
-    const float* __restrict__ dL_dsig2 = nullptr, float* __restrict__ stash = nullptr,
-    const float* __restrict__ xyzs = nullptr, const float* __restrict__ w_master = nullptr,
-    float* __restrict__ dL_ddirs = nullptr) {
+    const float* __restrict__ dL_dsig2, float* __restrict__ stash, const float* __restrict__ xyzs,
+    const float* __restrict__ w_master, float* __restrict__ dL_ddirs) {
     static_assert(!DIN || PART == BWD_ALL, "the direction gradient leaves the one-pass form only");
     typedef typename Mfma<T>::v4 v4;
+    if (rgb_on && *rgb_on == 0.f) dL_drgb = nullptr;  // (uniform; bwd_load then leaves dr0..2 at zero)
     // AMP loss scale (GradScaler of the reference's precision=16 run) times tcnn's fp16 module loss
     // scale (128): the fp16 chain sees the upstream gradients times S (a power of two), dE and dW
     // leave it divided by S.  bf16 (fp32's exponent range) runs unscaled, as tcnn's non-fp16 modules.
@@ -417,7 +433,7 @@ __global__ __launch_bounds__(BWD_THREADS, PART == BWD_SIGMA ? 4 : 2) void field_
     const DeWs ws(n);  // the dE workspace (field_de_ws.h): header, [16][e_stride] pairs, positions, queue
     const int64_t n_stride = ws.e_stride;
     float* const dE_pairs = dE_out ? dE_out + ws.row(0) : nullptr;
-    if (PART != BWD_RGB && dE_out && blockIdx.x == 0 && threadIdx.x < SC_QUEUE_WORDS) {
+    if (PART != BWD_RGB && dE_out && bid == 0 && threadIdx.x < SC_QUEUE_WORDS) {
         if (threadIdx.x == 0) {
             dE_out[DeWs::INV_S] = inv_S;
             dE_out[DeWs::OPERAND] = Mfma<T>::f16 ? 0.f : 1.f;
@@ -430,7 +446,7 @@ __global__ __launch_bounds__(BWD_THREADS, PART == BWD_SIGMA ? 4 : 2) void field_
     const float* pos_src = ((PART & DE_POS_PART) != 0 && dE_out && !order) ? xyzs : nullptr;
     float* const pos_out = pos_src ? dE_out + ws.positions() : nullptr;
     const int64_t pos_stride = ws.pos_stride();
-    if ((PART & DE_POS_PART) != 0 && dE_out && blockIdx.x == 0 && threadIdx.x == 0)
+    if ((PART & DE_POS_PART) != 0 && dE_out && bid == 0 && threadIdx.x == 0)
         dE_out[DeWs::POS_MASK] = pos_out ? (float)((1 << DE_POS_MLP_CLASSES) - 1) : 0.f;
     const int lm_rows = bwd_blocks_of(n);            // level_max rows the scatter reads
     // split passes' stash (ncn_field_bwd_stash_floats): [groups][64] operand tiles, then [groups][16]
@@ -439,18 +455,13 @@ __global__ __launch_bounds__(BWD_THREADS, PART == BWD_SIGMA ? 4 : 2) void field_
     float* sth0 = stash ? stash + ((n + 15) / 16) * 128 : nullptr;
     const int64_t n_cap = n;
     if (n_dev) n = min<int64_t>(n, *n_dev);
-    // the sigma pass keeps only the sigma_net fragments and its 11 exchange tiles per group (57 KB:
-    // two workgroups per CU); the others all 34 + 8 fragments and 30 tiles (158 KB)
     constexpr bool SIGONLY = PART == BWD_SIGMA;
-    constexpr int NF32 = SIGONLY ? N_SIG32 : N_FRAG32, NF16 = SIGONLY ? N_SIG16 : N_FRAG16, NX = x_count<PART>();
-    __shared__ v8 F32s[NF32 * 64];
-    __shared__ v4 F16s[NF16 * 64];
-    __shared__ __attribute__((aligned(16))) uint16_t X[BWD_WAVES * NX * 256];  // dW operand images
+    constexpr int NF32 = BwdLds<T, PART>::NF32, NF16 = BwdLds<T, PART>::NF16, NX = BwdLds<T, PART>::NX;
     SG_TREAL(6);
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int64_t n_groups = (n + 15) / 16;
-    const int64_t stride = (int64_t)gridDim.x * BWD_WAVES;
-    int64_t base = (int64_t)blockIdx.x * BWD_WAVES;  // first group of this workgroup's step
+    const int64_t stride = (int64_t)nblk * BWD_WAVES;
+    int64_t base = (int64_t)bid * BWD_WAVES;  // first group of this workgroup's step
     BwdIn<T> nxt;
     // (sigma pass: the first step's loads leave before the fragments are staged, so the two latencies
     // overlap; the other passes keep their registers free until the loop)
@@ -469,7 +480,7 @@ __global__ __launch_bounds__(BWD_THREADS, PART == BWD_SIGMA ? 4 : 2) void field_
         for (int i = threadIdx.x; i < NF16 * 64; i += BWD_THREADS) F16s[i] = w16[(SIGONLY ? B_L2 * 64 : 0) + i];
     }
     if constexpr (PART == BWD_RGB) {  // the sigma pass max-reduces into the level_max rows: zero them
-        if (blockIdx.x == 0 && level_max)
+        if (bid == 0 && level_max)
             for (int i = threadIdx.x; i < lm_rows * 16; i += BWD_THREADS) level_max[i] = 0.f;
     }
     DinCtx<T> din = {nullptr, order, dL_ddirs};
@@ -478,8 +489,8 @@ __global__ __launch_bounds__(BWD_THREADS, PART == BWD_SIGMA ? 4 : 2) void field_
         for (int i = threadIdx.x; i < 3 * 64; i += BWD_THREADS) W3d[i] = (T)w_master[W3_OFF + (i & 63) * 32 + (i >> 6)];
         din.w3d = W3d;
         // the rows past the device count leave as zeros
-        for (int64_t i = 3 * n + (int64_t)blockIdx.x * BWD_THREADS + threadIdx.x; i < 3 * n_cap;
-             i += (int64_t)gridDim.x * BWD_THREADS)
+        for (int64_t i = 3 * n + (int64_t)bid * BWD_THREADS + threadIdx.x; i < 3 * n_cap;
+             i += (int64_t)nblk * BWD_THREADS)
             dL_ddirs[i] = 0.f;
     }
     __syncthreads();
@@ -550,8 +561,8 @@ __global__ __launch_bounds__(BWD_THREADS, PART == BWD_SIGMA ? 4 : 2) void field_
         SG_TADD(5, 0ull, 1ull);
     }
     SG_TREAL(8);
-    bwd_store_dw<PART>(slab + (int64_t)blockIdx.x * NCN_FIELD_NW, wid, lane, acc, inv_S);
-    if constexpr (PART == BWD_RGB) return;  // (no encoding gradient in the rgb pass)
+    bwd_store_dw<PART>(slab + (int64_t)bid * NCN_FIELD_NW, wid, lane, acc, inv_S);
+    if constexpr (PART == BWD_RGB) return;  // (no encoding gradient in the rgb pass: lmw is never allocated)
     // level maxima: the 16 lanes of a row (same g) share their 4 levels; the row leaders of the 8
     // waves meet in LDS and the workgroup writes its row of level_max [blocks][16] (no atomics: the
     // scatter reduces the rows)
@@ -579,14 +590,33 @@ __global__ __launch_bounds__(BWD_THREADS, PART == BWD_SIGMA ? 4 : 2) void field_
         for (int w = 0; w < BWD_WAVES; w++) m = fmaxf(m, lmw[w][threadIdx.x]);
         if constexpr (PART == BWD_SIGMA)  // (any grid size: rows zeroed by the rgb pass; m >= 0, so the
             // IEEE order is the unsigned order of the bits)
-            atomicMax((unsigned*)&level_max[(blockIdx.x % lm_rows) * 16 + threadIdx.x], __float_as_uint(m));
+            atomicMax((unsigned*)&level_max[(bid % lm_rows) * 16 + threadIdx.x], __float_as_uint(m));
         else
-            level_max[blockIdx.x * 16 + threadIdx.x] = m;
+            level_max[bid * 16 + threadIdx.x] = m;
     }
     // a capped grid (ncn_field_bwd_mlp_part's n_blocks) leaves the scatter's remaining rows neutral
-    if (PART == BWD_ALL && blockIdx.x == 0)
-        for (int i = (int)gridDim.x * 16 + threadIdx.x; i < lm_rows * 16; i += BWD_THREADS) level_max[i] = 0.f;
+    if (PART == BWD_ALL && bid == 0)
+        for (int i = nblk * 16 + threadIdx.x; i < lm_rows * 16; i += BWD_THREADS) level_max[i] = 0.f;
     SG_TREAL(9);
+}
+
+// (the sigma pass runs two workgroups per CU: 4 waves per SIMD, so at most 128 VGPRs)
+template <typename T, int PART = BWD_ALL, bool DIN = false>
+__global__ __launch_bounds__(BWD_THREADS, PART == BWD_SIGMA ? 4 : 2) void field_bwd_kernel(
+    const float* __restrict__ dirs, int64_t n, const int32_t* __restrict__ n_dev, const uint16_t* __restrict__ wpacked,
+    const typename Mfma<T>::v8* __restrict__ enc_cache, const float* __restrict__ dL_dsig,
+    const float* __restrict__ dL_drgb, const float* __restrict__ loss_scale, float* __restrict__ dE_out,
+    float* __restrict__ slab, float* __restrict__ level_max, const int32_t* __restrict__ order,
+    const float* __restrict__ dL_dsig2 = nullptr, float* __restrict__ stash = nullptr,
+    const float* __restrict__ xyzs = nullptr, const float* __restrict__ w_master = nullptr,
+    float* __restrict__ dL_ddirs = nullptr) {
+    typedef BwdLds<T, PART> Lds;
+    __shared__ typename Mfma<T>::v8 F32s[Lds::NF32 * 64];
+    __shared__ typename Mfma<T>::v4 F16s[Lds::NF16 * 64];
+    __shared__ __attribute__((aligned(16))) uint16_t X[BWD_WAVES * Lds::NX * 256];
+    field_bwd_body<T, PART, DIN>(F32s, F16s, X, (int)blockIdx.x, (int)gridDim.x, nullptr, dirs, n, n_dev, wpacked, enc_cache,
+                                 dL_dsig, dL_drgb, loss_scale, dE_out, slab, level_max, order, dL_dsig2, stash, xyzs,
+                                 w_master, dL_ddirs);
 }
 
 // Sum of the per-workgroup dW slabs: blockIdx.y takes a chunk of slabs (coalesced 1 KB rows),
@@ -594,7 +624,7 @@ __global__ __launch_bounds__(BWD_THREADS, PART == BWD_SIGMA ? 4 : 2) void field_
 constexpr int WRED_CHUNK = 16;
 // (nb_sigma rows of the sigma_net weights W1, W2 and nb_rgb rows of the rgb_net's: the split
 // backward's two passes run on grids of their own)
-__global__ void reduce_wgrad_kernel(const float* __restrict__ slab, int nb_sigma, int nb_rgb, float* __restrict__ gw) {
+inline __global__ void reduce_wgrad_kernel(const float* __restrict__ slab, int nb_sigma, int nb_rgb, float* __restrict__ gw) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= NCN_FIELD_NW) return;
     const int nb = i < W3_OFF ? nb_sigma : nb_rgb;

@@ -113,7 +113,7 @@ __device__ float frag32_value(const float* __restrict__ W, int f, int lane, int 
 __device__ float frag16_value(const float* __restrict__ W, int f, int lane, int j) { return W[frag16_index(f, lane, j)]; }
 
 // packed position -> master weight index (ncn_field_pack_map)
-__global__ void pack_map_kernel(int32_t* __restrict__ src) {
+inline __global__ void pack_map_kernel(int32_t* __restrict__ src) {
     const int f = blockIdx.x, lane = threadIdx.x;
     if (f < N_FRAG32) {
         for (int j = 0; j < 8; j++) src[(f * 64 + lane) * 8 + j] = frag32_index(f, lane, j);

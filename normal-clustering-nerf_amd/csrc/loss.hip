@@ -101,16 +101,8 @@ int ncn_photo_normals_count_fwd(const float* rgb, const float* rgb_gt, const flo
                        dim3(PH_THREADS), 0, (hipStream_t)stream, rgb, rgb_gt, opacity, n_rays, w_opacity, loss, rays_o,
                        rays_d, depth, x1, x2, x3, n_tri, normals, total_samples, n_count, counter, count_out,
                        count_acc);
-    NCN_LAUNCH_CHECK("ncn_photo_normals_fwd");
+    NCN_LAUNCH_CHECK("ncn_photo_normals_count_fwd");
     return 0;
-}
-
-int ncn_photo_normals_fwd(const float* rgb, const float* rgb_gt, const float* opacity, int64_t n_rays,
-                          float w_opacity, float* loss, const float* rays_o, const float* rays_d, const float* depth,
-                          const int64_t* x1, const int64_t* x2, const int64_t* x3, int64_t n_tri, float* normals,
-                          void* stream) {
-    return ncn_photo_normals_count_fwd(rgb, rgb_gt, opacity, n_rays, w_opacity, loss, rays_o, rays_d, depth, x1, x2,
-                                       x3, n_tri, normals, nullptr, 0, nullptr, nullptr, nullptr, stream);
 }
 
 int ncn_normals_fwd(const float* rays_o, const float* rays_d, const float* depth, const int64_t* x1, const int64_t* x2,

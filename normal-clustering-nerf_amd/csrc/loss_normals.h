@@ -29,7 +29,7 @@ __device__ __forceinline__ void normals_fwd_one(const float* __restrict__ o, con
     normals[3 * t + 2] = c2 / nrm;
 }
 
-__global__ void normals_fwd_kernel(const float* __restrict__ o, const float* __restrict__ d,
+inline __global__ void normals_fwd_kernel(const float* __restrict__ o, const float* __restrict__ d,
                                    const float* __restrict__ depth, const int64_t* __restrict__ x1,
                                    const int64_t* __restrict__ x2, const int64_t* __restrict__ x3, int64_t T,
                                    float* __restrict__ normals) {
@@ -79,7 +79,7 @@ __device__ __forceinline__ void tri_normal_grad(const float* __restrict__ dn, co
     }
 }
 
-__global__ void normals_bwd_kernel(const float* __restrict__ o, const float* __restrict__ d,
+inline __global__ void normals_bwd_kernel(const float* __restrict__ o, const float* __restrict__ d,
                                    const float* __restrict__ depth, const int64_t* __restrict__ x1,
                                    const int64_t* __restrict__ x2, const int64_t* __restrict__ x3, int64_t T,
                                    const float* __restrict__ dn, const float* __restrict__ tw,
@@ -98,7 +98,7 @@ __global__ void normals_bwd_kernel(const float* __restrict__ o, const float* __r
 // The same backward with the rays' gradients (camera pose refinement: rays_o / rays_d require
 // grad): dL/dP1 = -(da + db), dL/dP2 = da, dL/dP3 = db through P = o + d * depth, so per corner
 // dL/do += dL/dP, dL/dd += depth * dL/dP, dL/ddepth += d . dL/dP (the sums of ncn_normals_bwd).
-__global__ void normals_bwd_rays_kernel(const float* __restrict__ o, const float* __restrict__ d,
+inline __global__ void normals_bwd_rays_kernel(const float* __restrict__ o, const float* __restrict__ d,
                                         const float* __restrict__ depth, const int64_t* __restrict__ x1,
                                         const int64_t* __restrict__ x2, const int64_t* __restrict__ x3, int64_t T,
                                         const float* __restrict__ dn, const float* __restrict__ tw,

@@ -37,7 +37,7 @@ __device__ __forceinline__ void photo_loss_fwd_wg(const float* __restrict__ rgb,
     }
 }
 
-__global__ __launch_bounds__(PH_THREADS) void photo_loss_fwd_kernel(const float* __restrict__ rgb,
+inline __global__ __launch_bounds__(PH_THREADS) void photo_loss_fwd_kernel(const float* __restrict__ rgb,
                                                                     const float* __restrict__ gt,
                                                                     const float* __restrict__ op, int64_t R,
                                                                     float w_op, float* __restrict__ loss) {
@@ -49,26 +49,41 @@ __global__ __launch_bounds__(PH_THREADS) void photo_loss_fwd_kernel(const float*
 // fused loss node.
 // With cnt_total: one more workgroup (block 1) sums the compositor's per-ray sample counts (the
 // vr_samples of the render, ncn_count_samples' work) beside them instead of in a launch of its own.
-__global__ __launch_bounds__(PH_THREADS) void photo_normals_fwd_kernel(
+// (workgroup bid of the launch; a device function so that a wider launch can append workgroups of
+// its own behind these, split_fused.hip)
+__device__ __forceinline__ void photo_normals_fwd_wg(
+    const int bid, const float* __restrict__ rgb, const float* __restrict__ gt, const float* __restrict__ op, int64_t R,
+    float w_op, float* __restrict__ loss, const float* __restrict__ o, const float* __restrict__ d,
+    const float* __restrict__ depth, const int64_t* __restrict__ x1, const int64_t* __restrict__ x2,
+    const int64_t* __restrict__ x3, int64_t T, float* __restrict__ normals, const int64_t* __restrict__ cnt_total,
+    int64_t cnt_n, const int32_t* __restrict__ cnt_counter, int64_t* __restrict__ cnt_out, double* __restrict__ cnt_acc) {
+    if (bid == 0) {
+        photo_loss_fwd_wg(rgb, gt, op, R, w_op, loss);
+        return;
+    }
+    const int nb0 = cnt_total ? 2 : 1;  // workgroups in front of the normals
+    if (cnt_total && bid == 1) {
+        count_samples_wg(cnt_total, cnt_n, cnt_counter, cnt_out, cnt_acc);
+        return;
+    }
+    const int64_t t = (int64_t)(bid - nb0) * PH_THREADS + threadIdx.x;
+    if (t < T) normals_fwd_one(o, d, depth, x1, x2, x3, t, normals);
+}
+inline __global__ __launch_bounds__(PH_THREADS) void photo_normals_fwd_kernel(
     const float* __restrict__ rgb, const float* __restrict__ gt, const float* __restrict__ op, int64_t R, float w_op,
     float* __restrict__ loss, const float* __restrict__ o, const float* __restrict__ d,
     const float* __restrict__ depth, const int64_t* __restrict__ x1, const int64_t* __restrict__ x2,
     const int64_t* __restrict__ x3, int64_t T, float* __restrict__ normals, const int64_t* __restrict__ cnt_total,
     int64_t cnt_n, const int32_t* __restrict__ cnt_counter, int64_t* __restrict__ cnt_out, double* __restrict__ cnt_acc) {
-    if (blockIdx.x == 0) {
-        photo_loss_fwd_wg(rgb, gt, op, R, w_op, loss);
-        return;
-    }
-    const int nb0 = cnt_total ? 2 : 1;  // workgroups in front of the normals
-    if (cnt_total && blockIdx.x == 1) {
-        count_samples_wg(cnt_total, cnt_n, cnt_counter, cnt_out, cnt_acc);
-        return;
-    }
-    const int64_t t = (int64_t)(blockIdx.x - nb0) * PH_THREADS + threadIdx.x;
-    if (t < T) normals_fwd_one(o, d, depth, x1, x2, x3, t, normals);
+    photo_normals_fwd_wg((int)blockIdx.x, rgb, gt, op, R, w_op, loss, o, d, depth, x1, x2, x3, T, normals, cnt_total,
+                         cnt_n, cnt_counter, cnt_out, cnt_acc);
+}
+// dL/drgb of one channel: ga = the upstream gradient times the term's validity flag, sa = 2 / (3 R)
+__device__ __forceinline__ float photo_drgb(float ga, float sa, float rgb, float gt) {
+    return ga == 0.f ? 0.f : ga * sa * (rgb - gt);
 }
 // grads scaled by the upstream gradient g[0..1] (device scalars) and zeroed for filtered terms
-__global__ void photo_loss_bwd_kernel(const float* __restrict__ rgb, const float* __restrict__ gt,
+inline __global__ void photo_loss_bwd_kernel(const float* __restrict__ rgb, const float* __restrict__ gt,
                                       const float* __restrict__ op, int64_t R, float w_op,
                                       const float* __restrict__ loss, const float* __restrict__ g,
                                       float* __restrict__ drgb, float* __restrict__ dop) {
@@ -90,7 +105,7 @@ __global__ void photo_loss_bwd_kernel(const float* __restrict__ rgb, const float
 //   [i >= 1, j <= 6]; triangle (i,j) of patch p is index p*49 + 7(i-1) + (j-1).
 // Upstream gradients: up_total (the `total` output) + up_terms[5] (rgb, opacity, ort, centr_dot,
 // centr_L1 outputs), either may be NULL (= 0).
-__global__ void nerf_loss_bwd_kernel(const float* __restrict__ rgb, const float* __restrict__ gt,
+inline __global__ void nerf_loss_bwd_kernel(const float* __restrict__ rgb, const float* __restrict__ gt,
                                      const float* __restrict__ op, int64_t R, float w_op,
                                      const float* __restrict__ photo, const float* __restrict__ o,
                                      const float* __restrict__ d, const float* __restrict__ depth,
@@ -108,7 +123,7 @@ __global__ void nerf_loss_bwd_kernel(const float* __restrict__ rgb, const float*
         const float ga = u[0] * photo[2], gb = u[1] * photo[3];
         const float sa = 2.f / (float)(3 * R);
 #pragma unroll
-        for (int c = 0; c < 3; c++) drgb[3 * ray + c] = ga == 0.f ? 0.f : ga * sa * (rgb[3 * ray + c] - gt[3 * ray + c]);
+        for (int c = 0; c < 3; c++) drgb[3 * ray + c] = photo_drgb(ga, sa, rgb[3 * ray + c], gt[3 * ray + c]);
         const float oo = op[ray] + 1e-10f;
         dop[ray] = gb == 0.f ? 0.f : gb * w_op * (-(logf(oo) + 1.f)) / (float)R;
     }

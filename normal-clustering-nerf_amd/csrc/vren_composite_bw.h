@@ -11,7 +11,10 @@ namespace ncn {
 // follows :349-359.  All of the block's loads are issued up front; the product scans run
 // interleaved, the prefix sums of (w*t, w*raw_0..2) as one 4-way DPP scan per row; carries chain
 // through readlane.  DWS: a non-NULL dL_dws (the reference's is a zero tensor in training, q5).
-template <int C, int ROWS, bool GUARD, bool DWS>
+// DSIG = false (the split step's early dL/draws, split_fused.hip): only dL_draws = dL_drend * w is
+// formed — the dL/dsigma terms, their loads (ts, raws) and their stores are compiled out; w itself
+// (alpha, the transmittance chain, the stop) is the same code.
+template <int C, int ROWS, bool GUARD, bool DWS, bool DSIG = true>
 __device__ __forceinline__ bool composite_bw_block(
     const __amdgpu_buffer_rsrc_t& r_s, const __amdgpu_buffer_rsrc_t& r_d, const __amdgpu_buffer_rsrc_t& r_t,
     const __amdgpu_buffer_rsrc_t& r_r, const __amdgpu_buffer_rsrc_t& r_dw, const __amdgpu_buffer_rsrc_t& r_ws,
@@ -25,9 +28,9 @@ __device__ __forceinline__ bool composite_bw_block(
         if (!GUARD || r == 0 || base + r * 64 < N) {
             sg[r] = buf_load(r_s, k * 4u);
             dl[r] = buf_load(r_d, k * 4u);
-            tt[r] = buf_load(r_t, k * 4u);
+            tt[r] = DSIG ? buf_load(r_t, k * 4u) : 0.f;
 #pragma unroll
-            for (int i = 0; i < C; i++) rr[r][i] = buf_load(r_r, k * (4u * C) + 4u * i);
+            for (int i = 0; i < C; i++) rr[r][i] = DSIG ? buf_load(r_r, k * (4u * C) + 4u * i) : 0.f;
             dws[r] = DWS ? buf_load(r_dw, k * 4u) : 0.f;
             pw[r] = DWS ? dws[r] * buf_load(r_ws, k * 4u) : 0.f;
         } else {
@@ -63,6 +66,13 @@ __device__ __forceinline__ bool composite_bw_block(
     for (int r = 0; r < ROWS; r++) {
         const bool inc = r < srow || (r == srow && lane <= slane);
         const float w = inc ? a[r] * Tb[r] : 0.f;
+        if constexpr (!DSIG) {
+            if (!GUARD || r == 0 || base + r * 64 < N) {
+#pragma unroll
+                for (int i = 0; i < C; i++) buf_store(r_gr, (uint32_t)(base + r * 64 + lane) * (4u * C) + 4u * i, dR[i] * w);
+            }
+            continue;
+        }
         // inclusive prefixes (this row + carry) of w*t, w*raw_i, dL_dws*ws
         // (this row body is composite_bw_coop's too: as one forceinline function it moved four register lines, <1, false> 58 -> 64 VGPRs)
         float run_d = w * tt[r], run_r[C];
@@ -94,7 +104,7 @@ __device__ __forceinline__ bool composite_bw_block(
     }
     if (srow < ROWS) {  // rest of the segment: zero gradients
         for (int k = base + ROWS * 64 + lane; k < N; k += 64) {
-            buf_store(r_gs, (uint32_t)k * 4u, 0.f);
+            if (DSIG) buf_store(r_gs, (uint32_t)k * 4u, 0.f);
 #pragma unroll
             for (int i = 0; i < C; i++) buf_store(r_gr, (uint32_t)k * (4u * C) + 4u * i, 0.f);
         }
@@ -105,25 +115,28 @@ __device__ __forceinline__ bool composite_bw_block(
 
 // Backward (volumerendering.cu:297-418): same block structure as the forward (1/2/4-row blocks for
 // N <= 256, guarded 4-row blocks beyond).  A NULL upstream gradient skips its term.
-template <int C, bool DWS>
+// (DSIG = false: dL_drend is the ray's C values themselves, not the per-ray array, and only sigmas,
+// deltas and dL_draws are touched)
+template <int C, bool DWS, bool DSIG = true>
 __device__ __forceinline__ void composite_bw_ray(
     const float* __restrict__ dL_dopacity, const float* __restrict__ dL_ddepth, const float* __restrict__ dL_drend,
     const float* __restrict__ dL_dws, const float* __restrict__ sigmas, const float* __restrict__ raws,
     const float* __restrict__ ws, const float* __restrict__ deltas, const float* __restrict__ ts, const RaySeg& g,
     const float* __restrict__ opacity, const float* __restrict__ depth, const float* __restrict__ rend,
     float T_thr, float* __restrict__ dL_dsigmas, float* __restrict__ dL_draws, float bg) {
+    static_assert(DSIG || !DWS, "the draws-only form has no dL_dws term");
     const int lane = threadIdx.x & 63;
     const int N = g.N;
     const int64_t ray = g.ray;
     // (this per-ray prologue is composite_bw_coop's too: behind one struct + loader <3, false> went from 99 to 95 SGPRs)
-    const float dO = dL_dopacity ? dL_dopacity[ray] : 0.f;
-    const float dD = dL_ddepth ? dL_ddepth[ray] : 0.f;
-    const float O = opacity[ray], D = depth[ray];
+    const float dO = DSIG && dL_dopacity ? dL_dopacity[ray] : 0.f;
+    const float dD = DSIG && dL_ddepth ? dL_ddepth[ray] : 0.f;
+    const float O = DSIG ? opacity[ray] : 0.f, D = DSIG ? depth[ray] : 0.f;
     float dR[C], RE[C];
 #pragma unroll
     for (int i = 0; i < C; i++) {
-        dR[i] = dL_drend ? dL_drend[ray * C + i] : 0.f;
-        RE[i] = rend[ray * C + i];
+        dR[i] = !DSIG ? dL_drend[i] : dL_drend ? dL_drend[ray * C + i] : 0.f;
+        RE[i] = DSIG ? rend[ray * C + i] : 0.f;
     }
     // with the background folded in (rgb = rend + bg * (1 - O)): dL/drend = dL/drgb and the opacity
     // picks up -bg * sum_i dL/drgb_i (the reference's autograd through rendering.py:236)
@@ -135,8 +148,9 @@ __device__ __forceinline__ void composite_bw_ray(
     const float gO = dOe * (1 - O);
     const uint32_t nb = (uint32_t)N * 4u;
     const auto r_s = buf_rsrc(sigmas + g.start, nb), r_d = buf_rsrc(deltas + g.start, nb);
-    const auto r_t = buf_rsrc(ts + g.start, nb), r_r = buf_rsrc(raws + g.start * C, nb * C);
-    const auto r_gs = buf_rsrc(dL_dsigmas + g.start, nb), r_gr = buf_rsrc(dL_draws + g.start * C, nb * C);
+    const auto r_gr = buf_rsrc(dL_draws + g.start * C, nb * C);
+    const auto r_t = DSIG ? buf_rsrc(ts + g.start, nb) : r_s, r_r = DSIG ? buf_rsrc(raws + g.start * C, nb * C) : r_s;
+    const auto r_gs = DSIG ? buf_rsrc(dL_dsigmas + g.start, nb) : r_gr;  // (DSIG = false: never used)
     const auto r_dw = buf_rsrc(DWS ? dL_dws + g.start : dL_dsigmas, DWS ? nb : 0u);
     const auto r_ws = buf_rsrc(DWS ? ws + g.start : dL_dsigmas, DWS ? nb : 0u);
     float tot = 0.f;  // sum of dL_dws * ws over the whole segment
@@ -148,8 +162,8 @@ __device__ __forceinline__ void composite_bw_ray(
 #pragma unroll
     for (int i = 0; i < C; i++) cr[i] = 0.f;
 #define NCN_BW_BLOCK(ROWS, GUARD, BASE)                                                                    \
-    composite_bw_block<C, ROWS, GUARD, DWS>(r_s, r_d, r_t, r_r, r_dw, r_ws, r_gs, r_gr, BASE, N, T_thr, lane, gO, \
-                                            dD, D, tot, dR, RE, Tc, cd, cpw, cr)
+    composite_bw_block<C, ROWS, GUARD, DWS, DSIG>(r_s, r_d, r_t, r_r, r_dw, r_ws, r_gs, r_gr, BASE, N, T_thr, lane, \
+                                                  gO, dD, D, tot, dR, RE, Tc, cd, cpw, cr)
     if (N <= 64) {
         NCN_BW_BLOCK(1, false, 0);
     } else if (N <= 128) {
@@ -169,7 +183,8 @@ __device__ __forceinline__ void composite_bw_ray(
 // front of it (T_in = product of their products; prefix sums = their sums scaled by their T_in;
 // the stop cannot lie in front of the first stopping wave, so their sums are uncut), finds its
 // first stop, and after a second barrier the ray's first stop cuts w as in the single-wave rows.
-template <int C, bool DWS>
+// (DSIG = false: as composite_bw_ray's; the first CF_WPB waves of the workgroup take the ray)
+template <int C, bool DWS, bool DSIG = true>
 __device__ __forceinline__ void composite_bw_coop(
     const float* __restrict__ dL_dopacity, const float* __restrict__ dL_ddepth, const float* __restrict__ dL_drend,
     const float* __restrict__ dL_dws, const float* __restrict__ sigmas, const float* __restrict__ raws,
@@ -184,14 +199,14 @@ __device__ __forceinline__ void composite_bw_coop(
     const int N = (int)rays_a[3 * row + 2];
     if (N <= CF_LONG || N > CF_COOP_MAX) return;  // workgroup-uniform
     // (the per-ray prologue of composite_bw_ray: see there)
-    const float dO = dL_dopacity ? dL_dopacity[ray] : 0.f;
-    const float dD = dL_ddepth ? dL_ddepth[ray] : 0.f;
-    const float O = opacity[ray], D = depth[ray];
+    const float dO = DSIG && dL_dopacity ? dL_dopacity[ray] : 0.f;
+    const float dD = DSIG && dL_ddepth ? dL_ddepth[ray] : 0.f;
+    const float O = DSIG ? opacity[ray] : 0.f, D = DSIG ? depth[ray] : 0.f;
     float dR[C], RE[C];
 #pragma unroll
     for (int i = 0; i < C; i++) {
-        dR[i] = dL_drend ? dL_drend[ray * C + i] : 0.f;
-        RE[i] = rend[ray * C + i];
+        dR[i] = !DSIG ? dL_drend[i] : dL_drend ? dL_drend[ray * C + i] : 0.f;
+        RE[i] = DSIG ? rend[ray * C + i] : 0.f;
     }
     float dOe = dO;
     if (bg != 0.f) {
@@ -201,8 +216,9 @@ __device__ __forceinline__ void composite_bw_coop(
     const float gO = dOe * (1 - O);
     const uint32_t nb = (uint32_t)N * 4u;
     const auto r_s = buf_rsrc(sigmas + start, nb), r_d = buf_rsrc(deltas + start, nb);
-    const auto r_t = buf_rsrc(ts + start, nb), r_r = buf_rsrc(raws + start * C, nb * C);
-    const auto r_gs = buf_rsrc(dL_dsigmas + start, nb), r_gr = buf_rsrc(dL_draws + start * C, nb * C);
+    const auto r_gr = buf_rsrc(dL_draws + start * C, nb * C);
+    const auto r_t = DSIG ? buf_rsrc(ts + start, nb) : r_s, r_r = DSIG ? buf_rsrc(raws + start * C, nb * C) : r_s;
+    const auto r_gs = DSIG ? buf_rsrc(dL_dsigmas + start, nb) : r_gr;  // (DSIG = false: never used)
     const auto r_dw = buf_rsrc(DWS ? dL_dws + start : dL_dsigmas, DWS ? nb : 0u);
     const auto r_ws = buf_rsrc(DWS ? ws + start : dL_dsigmas, DWS ? nb : 0u);
     const int base = wv * 256;
@@ -212,9 +228,9 @@ __device__ __forceinline__ void composite_bw_coop(
         const uint32_t k = (uint32_t)(base + r * 64 + lane);
         sg[r] = buf_load(r_s, k * 4u);
         dl[r] = buf_load(r_d, k * 4u);
-        tt[r] = buf_load(r_t, k * 4u);
+        tt[r] = DSIG ? buf_load(r_t, k * 4u) : 0.f;
 #pragma unroll
-        for (int i = 0; i < C; i++) rr[r][i] = buf_load(r_r, k * (4u * C) + 4u * i);
+        for (int i = 0; i < C; i++) rr[r][i] = DSIG ? buf_load(r_r, k * (4u * C) + 4u * i) : 0.f;
         dws[r] = DWS ? buf_load(r_dw, k * 4u) : 0.f;
         pw[r] = DWS ? dws[r] * buf_load(r_ws, k * 4u) : 0.f;
     }
@@ -232,13 +248,14 @@ __device__ __forceinline__ void composite_bw_coop(
     for (int r = 0; r < 4; r++) {
         Tb[r] = Tl * wave_shr1_dpp(p[r], 1.0f);
         Tl = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Tb[r] * om[r]), 63));
+        if constexpr (!DSIG) continue;  // (only the product is carried)
         const float w = a[r] * Tb[r];
         ls[0] = fmaf(w, tt[r], ls[0]);
         ls[1] += pw[r];
 #pragma unroll
         for (int i = 0; i < C; i++) ls[2 + i] = fmaf(w, rr[r][i], ls[2 + i]);
     }
-    wave_sum_multi<2 + C>(ls);
+    if constexpr (DSIG) wave_sum_multi<2 + C>(ls);
     if (lane == 0) {
         sS[wv][0] = Tl;
 #pragma unroll
@@ -276,6 +293,13 @@ __device__ __forceinline__ void composite_bw_coop(
         const int pos = base + r * 64 + lane;  // (the row body of composite_bw_block, kept in step by hand: see there)
         const bool inc = pos <= stop;
         const float w = inc ? a[r] * Tb[r] : 0.f;
+        if constexpr (!DSIG) {
+            if (base + r * 64 < N) {
+#pragma unroll
+                for (int i = 0; i < C; i++) buf_store(r_gr, (uint32_t)pos * (4u * C) + 4u * i, dR[i] * w);
+            }
+            continue;
+        }
         float run_d = w * tt[r], run_r[C];
 #pragma unroll
         for (int i = 0; i < C; i++) run_r[i] = w * rr[r][i];

@@ -7,7 +7,18 @@ so the losses are bit-identical and the gradients agree up to f32 summation orde
 the order: the autograd backward can only start once the whole loss node (photometric + normals +
 the normal clustering, ~90 us of latency-bound k-means in 16 workgroups) has finished, while the
 photometric gradient does not depend on the clustering at all.  Here the photometric part is
-back-propagated on a side stream while the clustering runs:
+back-propagated while the clustering runs.  The fused sequence (the default) does it on one stream,
+with the rgb part of the field backward as a second role of the clustering's launch
+(ncn_split_loss_fused: no queue-to-queue fork and join around the clustering):
+
+  march -> field fwd -> composite fw
+        -> [photo + normals fwd | composite bw (rgb only: dL/draws)]     one launch
+        -> [cluster loss (k-means) | field MLP bwd, rgb part]             one launch
+        -> loss bwd (rgb, opacity, depth) -> composite bw (all terms)
+        -> field MLP bwd, sigma part -> table scatter (+ the dW slab reduction in the same launch)
+
+The forked sequence (SplitStep(fused=False)) is the same computation on two streams, kept as the
+reference of the fused one:
 
   main:  march -> field fwd -> composite fw -> photo+normals fwd -+-> cluster loss (k-means)
                                                                    |   -> loss bwd (depth)
@@ -15,7 +26,6 @@ back-propagated on a side stream while the clustering runs:
                                                                        -> composite bw (rgb)
                                                                        -> field MLP bwd, rgb part
   main (after the join): composite bw (all terms) -> field MLP bwd, sigma part -> table scatter
-                         (+ the dW slab reduction in the same launch)
 
 The rgb_net's input gradient dL/draws = w * dL/drgb needs only the photometric term, so the first
 composite backward yields it exactly as the joint one would; dL/dsigma mixes all three upstream
@@ -36,7 +46,7 @@ import torch
 
 from . import _lib, vren
 from ._lib import call
-from .losses import K_CLUSTERS, K_ITERS, _STD_OFFSETS, cluster_launch
+from .losses import K_CLUSTERS, K_ITERS, N_OUT, _STD_OFFSETS, _cluster_workspace, cluster_launch, kmeans_plan
 from .ngp_mt import N_W
 from .rendering import march_train_fused
 
@@ -76,17 +86,35 @@ def split_eligible(trainer, batch):
             and not any(isinstance(v, torch.Tensor) for k, v in kw.items() if k != "count_acc"))
 
 
+def _fused_loss(K, prec, rgb_blocks, rgb=None, rgb_gt=None, opacity=None, R=0, w_op=0.0, photo=None, rays_o=None,
+                rays_d=None, depth=None, x1=None, x2=None, x3=None, T=0, normals=None, total_s=None, counter=None,
+                cnt=None, acc=None, up_total=None, sigmas=None, deltas=None, rays_a=None, T_thr=0.0, draws=None,
+                niter=0, plan=None, t_sim=0.0, w=(0.0, 0.0, 0.0), step_dev=None, sched=(0.0, 1.0), out=None,
+                labels=None, cents=None, dn=None, workspace=None, xyzs=None, dirs=None, n=0, n_dev=None, order=None,
+                packed=None, enc=None, scale=None, slab=None, dE_ws=None, lmax=None, stash=None):
+    """ncn_split_loss_fused in its argument order.  With only (K, prec, rgb_blocks) nothing is
+    launched: the call is the co-residency check of the fused launch for that many rgb workgroups."""
+    call("ncn_split_loss_fused", rgb, rgb_gt, opacity, R, w_op, photo, rays_o, rays_d, depth, x1, x2, x3, T, normals,
+         total_s, counter, cnt, acc, up_total, sigmas, deltas, rays_a, T_thr, draws, K, niter, plan, t_sim, w[0], w[1],
+         w[2], None, step_dev, sched[0], sched[1], out, labels, cents, dn, workspace, xyzs, dirs, n, n_dev, order, packed,
+         prec, enc, scale, rgb_blocks, slab, dE_ws, lmax, stash)
+
+
 class SplitStep:
     """One training step (forward + split backward) of `trainer`'s model; run() is graph-capturable
     (no host reads).  Buffers that depend only on the batch size are allocated once."""
 
-    def __init__(self, trainer, rgb_blocks=None):
-        """rgb_blocks: the rgb pass's workgroups (one per CU), which run beside the clustering; by
+    def __init__(self, trainer, rgb_blocks=None, fused=True):
+        """fused: the clustering and the rgb pass as two roles of one launch on one stream
+        (ncn_split_loss_fused); False: the two on two streams (the forked sequence).
+        rgb_blocks: the rgb pass's workgroups (one per CU), which run beside the clustering; by
         default sized from the device (device_rgb_blocks: 240 on MI355X, fewer on a smaller part).
         The clustering's workgroups meet at grid barriers, so they must all stay resident on the CUs
         the rgb pass leaves: checked here (ncn_cluster_coresidency), before the step is captured — a
         configuration where they cannot is refused (NcnError) instead of spinning into the barrier
-        timeout, and Trainer then runs the autograd step.  (At N > 1
+        timeout, and Trainer then runs the autograd step.  Fused, a workgroup of either role takes a
+        CU, so the 16 + rgb_blocks workgroups of the launch must fit the device by count: checked here
+        as well (ncn_split_loss_fused with no rays is that check alone).  (At N > 1
         nothing else shares the step: the all-reduce of step k is stream-ordered before graph k+1,
         and RCCL's channels run beside the deferred coarse-level scatter, which leaves them 32 CUs,
         distributed.DP_SCATTER_BLOCKS.)"""
@@ -97,6 +125,9 @@ class SplitStep:
         cap = ctypes.c_int(0)
         call("ncn_cluster_coresidency", K_CLUSTERS, self.rgb_blocks, ctypes.byref(cap))
         self.cluster_capacity = cap.value
+        self.fused = bool(fused)
+        if self.fused:
+            _fused_loss(K_CLUSTERS, trainer.model._prec, self.rgb_blocks)
 
     def run(self, batch, step_dev, premarched=None):
         tr, m, L = self.tr, self.tr.model, self.tr.loss
@@ -126,9 +157,6 @@ class SplitStep:
         cnt = torch.empty((), dtype=torch.int64, device=dev)
         acc = kw.get("count_acc")
         rgb_gt = batch["rgb"].contiguous().float()
-        # (the normals use results["rays_o"] = rays_d, rendering.py:227 quirk q1)
-        call("ncn_photo_normals_count_fwd", rgb, rgb_gt, opacity, R, L.opacity_w, photo, rays_d, rays_d, depth, x1, x2,
-             x3, T, normals, total_s, R, n_dev if acc is not None else None, cnt, acc)
         w = (L.norm_D_C_ort_dot_w, L.norm_D_C_centr_dot_w, L.norm_D_C_centr_L1_w)
         one = tr._unit(dev)
         lib = _lib.lib()
@@ -146,8 +174,50 @@ class SplitStep:
             call("ncn_field_bwd_mlp_part", xyzs, dirs, n, n_dev, order, packed, m._prec, enc, dsig, None, drw, scale,
                  part, nb[part - 1], slab, dE_ws, lmax, stash)
 
-        # the photometric backward on a side stream (its first launch waits for the fork; the
-        # clustering, issued first on this stream, takes its CUs before the rgb pass fills the rest)
+        if self.fused:
+            # ---- photo + normals forward and dL/draws; the clustering and the rgb pass ----
+            out = torch.empty(N_OUT, dtype=torch.float32, device=dev)
+            labels = torch.empty(T, dtype=torch.int32, device=dev)
+            cents = torch.empty(K_CLUSTERS, 3, dtype=torch.float32, device=dev)
+            dn = torch.empty(3, T, 3, dtype=torch.float32, device=dev)
+            draws = torch.empty(n, 3, dtype=torch.float32, device=dev)
+            _fused_loss(K_CLUSTERS, m._prec, nb[0], rgb, rgb_gt, opacity, R, L.opacity_w, photo, rays_d, rays_d, depth, x1,
+                        x2, x3, T, normals, total_s, n_dev if acc is not None else None, cnt, acc, one, sigmas, deltas,
+                        rays_a, float(T_thr), draws, K_ITERS, kmeans_plan(dev, T, K_CLUSTERS, L.kmeans_seed),
+                        1.0 - L.norm_CAN_tres, w, step_dev, (float(L.can_sched_start), float(L._grow)), out, labels,
+                        cents, dn, _cluster_workspace(dev, K_CLUSTERS), xyzs, dirs, n, n_dev, order, packed, enc, scale,
+                        slab, dE_ws, lmax, stash)
+            # ---- loss backward (all three gradients) -> composite (all terms) -> field MLP (sigma part) ----
+            call("ncn_nerf_loss_bwd", rgb, rgb_gt, opacity, R, L.opacity_w, photo, rays_d, rays_d, depth, dn, one, None,
+                 drgb, dop, ddepth)
+        else:
+            # (the normals use results["rays_o"] = rays_d, rendering.py:227 quirk q1)
+            call("ncn_photo_normals_count_fwd", rgb, rgb_gt, opacity, R, L.opacity_w, photo, rays_d, rays_d, depth, x1,
+                 x2, x3, T, normals, total_s, R, n_dev if acc is not None else None, cnt, acc)
+            out, labels, cents, dn = self._forked(rgb, rgb_gt, opacity, R, photo, rays_d, depth, normals, w, step_dev,
+                                                  one, drgb, dop, ddepth, sigmas, rgbs, ws, deltas, ts, rays_a, rend,
+                                                  T_thr, mlp_part)
+        # dL/dsigma from all three upstream terms in one expression, as the autograd step's backward
+        dsig, _ = vren.composite_train_multi_bw(dop, ddepth, drgb, None, sigmas, rgbs, ws, deltas, ts, rays_a,
+                                                opacity, depth, rend, T_thr, bg=1.0)
+        mlp_part(2, dsig, None)
+        m._scatter(xyzs, n, n_dev, order, dE_ws, lmax, g_table, wgrad=(slab, nb[1], nb[0], g_w))
+        L.last_cluster = (labels, cents, out)
+        L.last_normals = normals
+        results = {"rays_a": rays_a, "deltas": deltas, "ts": ts, "rm_samples": n_dev, "vr_samples": cnt,
+                   "opacity": opacity, "depth": depth, "ws": ws, "rgb": rgb, "rays_d": rays_d, "rays_o": rays_d,
+                   "total_samples": total_s}
+        loss_d = {"rgb": photo[0], "opacity": photo[1], "norm_D_C_ort_dot": out[4], "norm_D_C_centr_dot": out[5],
+                  "norm_D_C_centr_L1": out[6], "total": out[10]}
+        return results, loss_d
+
+    def _forked(self, rgb, rgb_gt, opacity, R, photo, rays_d, depth, normals, w, step_dev, one, drgb, dop, ddepth,
+                sigmas, rgbs, ws, deltas, ts, rays_a, rend, T_thr, mlp_part):
+        """The forked sequence between the photometric forward and the joint compositor backward:
+        the photometric backward on a side stream (its first launch waits for the fork; the
+        clustering, issued first on this stream, takes its CUs before the rgb pass fills the rest)."""
+        tr, L = self.tr, self.tr.loss
+        dev = rgb.device
         cur = torch.cuda.current_stream(dev)
         side = tr._side_stream()
         side.wait_stream(cur)
@@ -165,16 +235,4 @@ class SplitStep:
         call("ncn_nerf_loss_bwd", rgb, rgb_gt, opacity, R, L.opacity_w, photo,
              rays_d, rays_d, depth, dn, one, None, None, None, ddepth)
         cur.wait_stream(side)
-        # dL/dsigma from all three upstream terms in one expression, as the autograd step's backward
-        dsig, _ = vren.composite_train_multi_bw(dop, ddepth, drgb, None, sigmas, rgbs, ws, deltas, ts, rays_a,
-                                                opacity, depth, rend, T_thr, bg=1.0)
-        mlp_part(2, dsig, None)
-        m._scatter(xyzs, n, n_dev, order, dE_ws, lmax, g_table, wgrad=(slab, nb[1], nb[0], g_w))
-        L.last_cluster = (labels, cents, out)
-        L.last_normals = normals
-        results = {"rays_a": rays_a, "deltas": deltas, "ts": ts, "rm_samples": n_dev, "vr_samples": cnt,
-                   "opacity": opacity, "depth": depth, "ws": ws, "rgb": rgb, "rays_d": rays_d, "rays_o": rays_d,
-                   "total_samples": total_s}
-        loss_d = {"rgb": photo[0], "opacity": photo[1], "norm_D_C_ort_dot": out[4], "norm_D_C_centr_dot": out[5],
-                  "norm_D_C_centr_L1": out[6], "total": out[10]}
-        return results, loss_d
+        return out, labels, cents, dn

@@ -53,7 +53,9 @@ class Trainer:
         "scannet_manhattan" = config #5).  split_backward (graph step; taken when the loss is the
         reference configuration, split_step.split_eligible): the step runs as split_step.SplitStep —
         the photometric backward overlaps the normal clustering, every per-sample value as the
-        autograd backward computes it — instead of render -> loss -> autograd backward."""
+        autograd backward computes it — instead of render -> loss -> autograd backward.  True or
+        "fused": the clustering and the rgb pass in one launch; "forked": on two streams
+        (SplitStep's `fused`)."""
         self.h = dict(hparams_for(preset), **(hparams or {}))
         self.model = model
         self.loss = NeRFMTLoss(self.h)
@@ -71,6 +73,7 @@ class Trainer:
                                   test_time=False, random_bg=False, anneal_strategy="none", anneal_steps=0)
         self.use_graph = use_graph
         self.split_backward = bool(split_backward) and use_graph
+        self.split_fused = split_backward != "forked"
         self._split = None  # the SplitStep of the captured graph (split_backward and split_eligible)
         self.graph = None
         # defer_optimizer (graph step): the optimizer step of step k runs inside graph k+1 on a side
@@ -174,7 +177,7 @@ class Trainer:
         self._split = None
         if self.split_backward and split_eligible(self, self._static):
             try:
-                self._split = SplitStep(self)
+                self._split = SplitStep(self, fused=self.split_fused)
             except _lib.NcnError as e:  # the clustering cannot stay resident beside the rgb pass
                 warnings.warn(f"split backward unavailable on this device, using the autograd step: {e}")
         self._step_dev = torch.zeros((), dtype=torch.int64, device=dev)
@@ -194,8 +197,20 @@ class Trainer:
         # the captured forward packs for itself unless the deferred optimizer in the body does it
         self.model._packed_fresh = False
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self._out = self._body(self._static, self._step_dev, self._with_opt)
+        # No cyclic garbage collection while the capture is open: a dead cycle that holds an earlier
+        # Trainer's CUDA graph and its memory pool is destroyed wherever the collector happens to run,
+        # and destroying a graph (or freeing its pool) on a capturing thread aborts the process.
+        # torch.cuda.graph no longer collects before it begins, so it is done here.
+        import gc
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(self.graph):
+                self._out = self._body(self._static, self._step_dev, self._with_opt)
+        finally:
+            if gc_was_on:
+                gc.enable()
         # the captured backward's deferred scatter names the graph's static buffers: every replay's
         # reduce_gradients(graph=True) runs that same entry; eager backwards keep their own list
         self.model._deferred_graph = self.model._deferred
