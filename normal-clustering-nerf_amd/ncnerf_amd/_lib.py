@@ -1,11 +1,13 @@
-"""ctypes binding of libncnerf.so, derived from the C ABI declared in include/ncnerf.h.
+"""ctypes binding of libncnerf.so, derived from the C ABI declared in include/ncnerf.h and, for the
+validation metrics, include/ncnerf_metrics.h.
 
 This is the only place Python talks to the HIP kernels.  There is NO CPU fallback: if the library
 is missing, or a kernel is called with a CPU tensor, the call raises.  Tensors are passed as raw
 device pointers and sizes, on torch's *current* HIP stream (never the legacy default stream).
 
-The header is the single statement of the ABI: parsed at import, it gives every argtypes / restype,
-and `call` marshals plain arguments against it (see `marshal`) before anything is launched.
+The headers are the single statement of the ABI: parsed at import into one table, they give every
+argtypes / restype, and `call` marshals plain arguments against it (see `marshal`) before anything
+is launched.
 """
 import ctypes
 import operator
@@ -17,6 +19,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NCN_LIB_PATH") or os.path.join(_HERE, "libncnerf.so")  # (override: diagnostics)
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "ncnerf.h")
+METRICS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ncnerf_metrics.h")  # same grammar, all `int`
 
 P = ctypes.c_void_p
 I64 = ctypes.c_int64
@@ -91,7 +94,25 @@ def _read_header():
         raise NcnError(f"include/ncnerf.h not found at {HEADER_PATH}: the binding is derived from it ({e})") from None
 
 
-ABI = parse_header(_read_header())
+def _read_metrics_header():
+    try:
+        return open(METRICS_HEADER_PATH).read()
+    except OSError as e:
+        raise NcnError(f"include/ncnerf_metrics.h not found at {METRICS_HEADER_PATH}: the binding of the "
+                       f"validation metrics is derived from it ({e})") from None
+
+
+def _parse_headers():
+    """One table from both headers; a name that both declare is an error."""
+    abi = parse_header(_read_header())
+    for name, decl in parse_header(_read_metrics_header()).items():
+        if name in abi:
+            raise NcnError(f"{name} is declared in both include/ncnerf.h and include/ncnerf_metrics.h")
+        abi[name] = decl
+    return abi
+
+
+ABI = _parse_headers()
 # name -> argtypes (stream last), as ctypes sees them
 SIGNATURES = dict((name, [P if kind == "ptr" else _SCALARS[kind] for kind, _, _ in params])
                   for name, (_, params) in ABI.items())

@@ -7,7 +7,8 @@
                                        ncn_kmeans_train (one workgroup) + ncn_kmeans_assign (stream)
   manhattan_frame                   <- train_nerf.py:503-513 (closest +-centroids, projection on SO(3))
   evaluate_views                    <- validation_step + validation_epoch_end: render, PSNR, normals
-                                       per view, ONE clustering over all views, the frame
+                                       per view, ONE clustering over all views, the frame; on request
+                                       val_metrics.update / compute (metrics.ViewMetrics)
 
 The k-means is the restatement of faiss's Clustering::train that oracle/losses_ref.py:spherical_kmeans
 states (faiss itself stays parity-unpinned, as for the training loss); the normals never leave the
@@ -198,7 +199,7 @@ def manhattan_frame(centrs_new, R_ref=None):
 
 
 def evaluate_views(model, poses, ray_dirs_cc, img_wh, rgb_gt=None, K=30, niter=30, t_similar=0.99, R_ref=None,
-                   **render_kwargs):
+                   depth_gt=None, normals_gt=None, metrics=False, **render_kwargs):
     """validation_step over every pose + validation_epoch_end's frame extraction.
 
     poses (V,3,4) or (V,4,4) camera-to-world, ray_dirs_cc (H*W,3), img_wh = (W, H), rgb_gt (V,H*W,3)
@@ -208,8 +209,21 @@ def evaluate_views(model, poses, ray_dirs_cc, img_wh, rgb_gt=None, K=30, niter=3
     (merge_clusters=True, find_opposite=False, as train_nerf.py:495-502).
     -> {"psnr": [per view] (empty without rgb_gt), "psnr_mean", "normals" (V,H,W,3), "labels"
     (clust_ass_new of the valid normals), "centroids" (3,3), "frame" (3,3 numpy), "angles"
-    (degrees to R_ref's columns, None without R_ref)}."""
+    (degrees to R_ref's columns, None without R_ref)}.
+
+    With metrics=True, depth_gt (V,H*W) or (V,H,W), or normals_gt (V,H*W,3) or (V,H,W,3) in world
+    coordinates, every view also goes through metrics.ViewMetrics (NeRFMTMetricsPerIm.update: the three
+    SSIMs; the depth errors with depth_gt; the angular errors of the depth-image normals with
+    normals_gt), which needs rgb_gt, and the result gains "metrics" (ViewMetrics.compute()'s log
+    keys) and "per_view" (one {column: value} per view).  The PSNRs are then column 0 of the rows, so
+    there is still one device-to-host copy outside the renderer and the clustering."""
+    from .metrics import COLUMNS, ViewMetrics
     from .rendering import render
+    vm = None
+    if metrics or depth_gt is not None or normals_gt is not None:
+        if rgb_gt is None:
+            raise ValueError("evaluate_views: the metrics need rgb_gt")
+        vm = ViewMetrics(eval_depth=depth_gt is not None, norm_gt=normals_gt is not None)
     W, H = int(img_wh[0]), int(img_wh[1])
     poses = poses.float()
     dirs = ray_dirs_cc.float().contiguous()
@@ -227,12 +241,28 @@ def evaluate_views(model, poses, ray_dirs_cc, img_wh, rgb_gt=None, K=30, niter=3
             res = render(model, rays_o, rays_d, **dict(kw))
             depth = res["depth"].reshape(1, H, W)
             normals[v] = extract_normals_from_depth_batch(depth, dirs, rot[None])[0]
-            if rgb_gt is not None:
+            if vm is not None:
+                rgb = res["rgb"].reshape(-1, 3).float().contiguous()
+                preds = {"rgb": rgb, "depth": res["depth"].reshape(-1).float().contiguous(),
+                         "norm_depth": normals[v].reshape(-1, 3)}
+                target = {"rgb": rgb_gt[v].reshape(-1, 3).to(rgb).contiguous()}
+                if depth_gt is not None:
+                    target["depth"] = depth_gt[v].reshape(-1).to(rgb).contiguous()
+                if normals_gt is not None:
+                    target["normals"] = normals_gt[v].reshape(-1, 3).to(rgb).contiguous()
+                vm.update(preds, target, H, W)
+            elif rgb_gt is not None:
                 mse = ((res["rgb"].reshape(-1, 3) - rgb_gt[v].reshape(-1, 3).to(res["rgb"])) ** 2).mean()
                 psnr.append(-10.0 * torch.log10(mse))
-        psnr = torch.stack(psnr).tolist() if psnr else []
+        extra = {}
+        if vm is not None:
+            rows = vm.rows().tolist()  # the one copy: V x 12 scalars
+            psnr = [r[0] for r in rows]
+            extra = {"metrics": vm.logs(rows), "per_view": [dict(zip(COLUMNS, r)) for r in rows]}
+        else:
+            psnr = torch.stack(psnr).tolist() if psnr else []
         labels, _, cents = normals_clustering(normals, K=K, niter=niter, t_similar=t_similar, merge_clusters=True,
                                               find_opposite=False)
     frame, angles = manhattan_frame(cents, R_ref)
     return {"psnr": psnr, "psnr_mean": (math.fsum(psnr) / len(psnr)) if psnr else None, "normals": normals,
-            "labels": labels, "centroids": cents, "frame": frame, "angles": angles}
+            "labels": labels, "centroids": cents, "frame": frame, "angles": angles, **extra}
