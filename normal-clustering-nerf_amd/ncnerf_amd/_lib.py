@@ -1,13 +1,14 @@
-"""ctypes binding of libncnerf.so, derived from the C ABI declared in include/ncnerf.h and, for the
-validation metrics, include/ncnerf_metrics.h.
+"""ctypes binding of libncnerf.so, derived from the C ABI declared in include/ncnerf.h, for the
+validation metrics in include/ncnerf_metrics.h, and for the geometry supervision (the depth, GT-normal
+and RegNeRF loss terms, the label gather) in include/ncnerf_geom.h.
 
 This is the only place Python talks to the HIP kernels.  There is NO CPU fallback: if the library
 is missing, or a kernel is called with a CPU tensor, the call raises.  Tensors are passed as raw
 device pointers and sizes, on torch's *current* HIP stream (never the legacy default stream).
 
-The headers are the single statement of the ABI: parsed at import into one table, they give every
-argtypes / restype, and `call` marshals plain arguments against it (see `marshal`) before anything
-is launched.
+The headers are the single statement of the ABI: parsed at import (ncnerf.h and ncnerf_metrics.h
+into the table ABI, ncnerf_geom.h into a table of its own, GEOM_ABI), they give every argtypes /
+restype, and `call` marshals plain arguments against them (see `marshal`) before anything is launched.
 """
 import ctypes
 import operator
@@ -20,6 +21,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NCN_LIB_PATH") or os.path.join(_HERE, "libncnerf.so")  # (override: diagnostics)
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "ncnerf.h")
 METRICS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ncnerf_metrics.h")  # same grammar, all `int`
+GEOM_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ncnerf_geom.h")  # same grammar, all `int`
 
 P = ctypes.c_void_p
 I64 = ctypes.c_int64
@@ -102,6 +104,14 @@ def _read_metrics_header():
                        f"validation metrics is derived from it ({e})") from None
 
 
+def _read_geom_header():
+    try:
+        return open(GEOM_HEADER_PATH).read()
+    except OSError as e:
+        raise NcnError(f"include/ncnerf_geom.h not found at {GEOM_HEADER_PATH}: the binding of the geometry "
+                       f"supervision is derived from it ({e})") from None
+
+
 def _parse_headers():
     """One table from both headers; a name that both declare is an error."""
     abi = parse_header(_read_header())
@@ -112,10 +122,33 @@ def _parse_headers():
     return abi
 
 
+def _parse_geom_header(abi):
+    """The third header's table; a name that `abi` (the first two headers) declares too is an error."""
+    geom = parse_header(_read_geom_header())
+    for name in geom:
+        if name in abi:
+            raise NcnError(f"{name} is declared in include/ncnerf_geom.h and in include/ncnerf.h or "
+                           f"include/ncnerf_metrics.h")
+    return geom
+
+
 ABI = _parse_headers()
+GEOM_ABI = _parse_geom_header(ABI)
+TABLES = (ABI, GEOM_ABI)
+
+
+def declaration(name):
+    """(restype, parameters) of an entry point, whichever header declares it."""
+    for table in TABLES:
+        decl = table.get(name)
+        if decl is not None:
+            return decl
+    raise KeyError(name)
+
+
 # name -> argtypes (stream last), as ctypes sees them
 SIGNATURES = dict((name, [P if kind == "ptr" else _SCALARS[kind] for kind, _, _ in params])
-                  for name, (_, params) in ABI.items())
+                  for table in TABLES for name, (_, params) in table.items())
 
 _lib = None
 
@@ -136,16 +169,17 @@ def lib():
             raise NcnError(f"libncnerf.so not found at {LIB_PATH}: run __graft_entry__.build() "
                            f"(make -C normal-clustering-nerf_amd)")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (ret, _) in ABI.items():
-            fn = getattr(L, name)
-            fn.argtypes = SIGNATURES[name]
-            fn.restype = _RESTYPES[ret]
+        for table in TABLES:
+            for name, (ret, _) in table.items():
+                fn = getattr(L, name)
+                fn.argtypes = SIGNATURES[name]
+                fn.restype = _RESTYPES[ret]
         _lib = L
     return _lib
 
 
 def exported_symbols():
-    return list(ABI)
+    return [name for table in TABLES for name in table]
 
 
 # ---- marshalling: one function per entry point, generated once from the header's parameters
@@ -160,7 +194,7 @@ def _launches(params):
 
 
 def _refuse(name, i, a):
-    params = ABI[name][1]
+    params = declaration(name)[1]
     kind, width, pname = params[i]
     expected = f"a host {kind}" if kind != "ptr" else (
         f"a {'CUDA ' if _launches(params) else ''}tensor{' of %d-byte elements' % width if width else ''}, "
@@ -209,7 +243,7 @@ def _marshaller(name, params):
     return ns["marshal"], (n - 1, n) if _launches(params) else (n,)
 
 
-_PLANS = {name: _marshaller(name, params) for name, (_, params) in ABI.items()}
+_PLANS = {name: _marshaller(name, params) for table in TABLES for name, (_, params) in table.items()}
 
 
 def marshal(name, args):
@@ -220,7 +254,7 @@ def marshal(name, args):
     without it: the current stream is appended, after every check.  Anything else is a TypeError."""
     fn, counts = _PLANS[name]
     if len(args) not in counts:
-        decl = ", ".join(f"{'pointer' if kind == 'ptr' else kind} {pname}" for kind, _, pname in ABI[name][1])
+        decl = ", ".join(f"{'pointer' if kind == 'ptr' else kind} {pname}" for kind, _, pname in declaration(name)[1])
         raise TypeError(f"{name}: takes {' or '.join(map(str, counts))} arguments, got {len(args)}: {name}({decl})")
     return fn(*args)
 

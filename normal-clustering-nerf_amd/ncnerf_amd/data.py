@@ -5,14 +5,15 @@ gather from the host image stack), the host-to-device copy of the batch, and the
 NeRFSystem.forward (train_nerf.py:167-182: poses[img_idxs], directions[pix_idxs], axisangle_to_R,
 get_rays) by two launches — ncn_batch_draw and ncn_batch_rays_fw — that read nothing from the host
 but a step counter, which may itself live on the device: with preallocated outputs they can be
-captured in a HIP graph.  The batch is the dict Trainer.step(batch, ...) takes; the Trainer itself
-does not draw from a dataset yet.  With optimize_ext the dataset holds the reference's per-image pose
-corrections dR (axis-angle) and dT (train_nerf.py:244-249) and the rays carry their gradient
-(ncn_batch_rays_bw, deterministic).
+captured in a HIP graph.  A dataset that was given label planes (depth, normals, normals_depth: the
+targets of NeRFMTLoss's depth and GT-normal terms) gathers them for the drawn rays in a third launch,
+ncn_batch_labels_fw, and its batches carry them under those keys.  The batch is the dict
+Trainer.step(batch, ...) takes; the Trainer itself does not draw from a dataset yet.
+With optimize_ext the dataset holds the reference's per-image pose corrections dR (axis-angle) and dT
+(train_nerf.py:244-249) and the rays carry their gradient (ncn_batch_rays_bw, deterministic).
 
-Only the two patch strategies are implemented (`all_images_triang_patch`, `same_image_triang_patch`);
-extra label planes (depth, normals) are not carried.  The draws are counter-based (seed, step, patch),
-not numpy's global generator.
+Only the two patch strategies are implemented (`all_images_triang_patch`, `same_image_triang_patch`).
+The draws are counter-based (seed, step, patch), not numpy's global generator.
 """
 import numpy as np
 import torch
@@ -56,6 +57,21 @@ def batch_rays_bw(g_o, g_d, img_idxs, pix_idxs, directions, poses, dR, grad_dR, 
          directions.shape[0], grad_dR, grad_dT)
 
 
+LABEL_PLANES = ("depth", "normals", "normals_depth")  # their widths: 1, 3, 3
+
+
+def batch_labels_fw(img_idxs, pix_idxs, planes, out):
+    """ncn_batch_labels_fw: out[k][r] = planes[k][img_idxs[r], pix_idxs[r]] for the planes that are there
+    (dicts keyed by LABEL_PLANES; depth (V, H*W), normals / normals_depth (V, H*W, 3)); an index out
+    of range gives NaN."""
+    given = [planes[k] for k in LABEL_PLANES if planes.get(k) is not None]
+    if not given:
+        return
+    call("ncn_batch_labels_fw", img_idxs, pix_idxs, img_idxs.numel(), planes.get("depth"), planes.get("normals"),
+         planes.get("normals_depth"), given[0].shape[0], given[0].shape[1],
+         *(out[k] if planes.get(k) is not None else None for k in LABEL_PLANES))
+
+
 class _PoseRays(torch.autograd.Function):
     """rays_o, rays_d, rgb of a drawn batch as a function of dR, dT (train_nerf.py:177-182)."""
 
@@ -84,16 +100,21 @@ class DeviceRayDataset:
     """images (V, H*W, 3) or (V, H, W, 3), float32 in [0, 1] or uint8; poses (V, 3, 4) camera-to-world;
     directions (H*W, 3) camera-space ray directions (get_ray_directions); img_wh = (W, H) as the
     reference's datasets keep it.  corner_mode "reference" keeps base.py:164-166's pixel arithmetic
-    (DESIGN.md §3), "grid" draws patches that lie inside the image."""
+    (DESIGN.md §3), "grid" draws patches that lie inside the image.  depth (V, H*W) or (V, H, W),
+    normals and normals_depth (V, H*W, 3) or (V, H, W, 3), float32: optional label planes, gathered
+    into every batch under their names."""
 
     def __init__(self, images, poses, directions, img_wh, batch_size=8192, patch_size=8,
-                 ray_sampling_strategy="all_images_triang_patch", seed=0, corner_mode="reference", optimize_ext=False):
+                 ray_sampling_strategy="all_images_triang_patch", seed=0, corner_mode="reference", optimize_ext=False,
+                 depth=None, normals=None, normals_depth=None):
         if ray_sampling_strategy not in STRATEGIES:
             raise ValueError(f"ray_sampling_strategy {ray_sampling_strategy!r} is not implemented on the device; "
                              f"one of {STRATEGIES}")
         if corner_mode not in CORNER_MODES:
             raise ValueError(f"corner_mode {corner_mode!r}; one of {sorted(CORNER_MODES)}")
-        for t, name in ((images, "images"), (poses, "poses"), (directions, "directions")):
+        planes = {k: t for k, t in zip(LABEL_PLANES, (depth, normals, normals_depth)) if t is not None}
+        for t, name in ((images, "images"), (poses, "poses"), (directions, "directions")) + tuple(
+                (t, k) for k, t in planes.items()):
             if not isinstance(t, torch.Tensor):
                 raise RuntimeError(f"{name} must be a CUDA tensor")
         W, H = int(img_wh[0]), int(img_wh[1])
@@ -114,17 +135,30 @@ class DeviceRayDataset:
             raise ValueError(f"poses must be ({V}, 3, 4) (got {tuple(poses.shape)})")
         if tuple(directions.shape) != (H * W, 3):
             raise ValueError(f"directions must be ({H * W}, 3) (got {tuple(directions.shape)})")
+        for k, t in planes.items():
+            _lib.check_dtype(t, torch.float32, k)
+            shape = (V, H * W) if k == "depth" else (V, H * W, 3)
+            full = (V, H, W) if k == "depth" else (V, H, W, 3)
+            if tuple(t.shape) == full:
+                planes[k] = t = t.reshape(shape)
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{k} must be {shape} for img_wh {(W, H)} (got {tuple(t.shape)})")
         patch_size, batch_size = int(patch_size), int(batch_size)
         if patch_size < 1 or patch_size > min(H, W):
             raise ValueError(f"patch_size {patch_size} does not fit a {W}x{H} image")
         if batch_size < 1 or batch_size % (patch_size * patch_size) != 0:
             raise ValueError(f"batch_size {batch_size} is not a multiple of patch_size^2 = {patch_size * patch_size}")
         # (the device last, so every check above also runs — and is tested — on a host without a GPU)
-        for t, name in ((images, "images"), (poses, "poses"), (directions, "directions")):
+        for t, name in ((images, "images"), (poses, "poses"), (directions, "directions")) + tuple(
+                (t, k) for k, t in planes.items()):
             _lib.check_input(t, name)
         if not (images.device == poses.device == directions.device):
             raise RuntimeError("images, poses and directions must be on one device")
+        for k, t in planes.items():
+            if t.device != images.device:
+                raise RuntimeError(f"{k} must be on the device of images")
         self.images, self.poses, self.directions = images, poses, directions
+        self.planes = planes  # the label planes that were given, by name
         self.H, self.W, self.n_images = H, W, V
         self.batch_size, self.patch_size = batch_size, patch_size
         self.n_patches = batch_size // (patch_size * patch_size)
@@ -140,13 +174,17 @@ class DeviceRayDataset:
             self.dR = torch.nn.Parameter(torch.zeros(V, 3, device=self.device))
             self.dT = torch.nn.Parameter(torch.zeros(V, 3, device=self.device))
 
-    def buffers(self, n_rays=None):
-        """Preallocated outputs of batch(out=...): the static batch buffers of a captured step."""
+    def buffers(self, n_rays=None, labels=True):
+        """Preallocated outputs of batch(out=...): the static batch buffers of a captured step, with
+        one buffer per label plane of the dataset unless labels is False."""
         n = self.batch_size if n_rays is None else n_rays
         f = dict(dtype=torch.float32, device=self.device)
         i = dict(dtype=torch.int64, device=self.device)
-        return {"rays_o": torch.empty(n, 3, **f), "rays_d": torch.empty(n, 3, **f), "rgb": torch.empty(n, 3, **f),
-                "img_idxs": torch.empty(n, **i), "pix_idxs": torch.empty(n, **i)}
+        out = {"rays_o": torch.empty(n, 3, **f), "rays_d": torch.empty(n, 3, **f), "rgb": torch.empty(n, 3, **f),
+               "img_idxs": torch.empty(n, **i), "pix_idxs": torch.empty(n, **i)}
+        for k in (self.planes if labels else ()):
+            out[k] = torch.empty((n,) if k == "depth" else (n, 3), **f)
+        return out
 
     def _rays(self, img_idxs, pix_idxs, out):
         if self.optimize_ext and torch.is_grad_enabled():
@@ -162,14 +200,19 @@ class DeviceRayDataset:
     def batch(self, step, out=None, seed=None):
         """The batch of `step` (an int or a device int64 scalar) as the dict Trainer.step and NeRFMTLoss
         take.  out: buffers() to write into (nothing is allocated: capturable); seed: overrides the
-        dataset's (data-parallel ranks draw with seed + rank).  No host read either way."""
+        dataset's (data-parallel ranks draw with seed + rank).  No host read either way.  The label
+        planes the dataset holds come with it under "depth" (n), "normals", "normals_depth" (n, 3)."""
         out = self.buffers() if out is None else out
         batch_draw(self.seed if seed is None else seed, step, self.n_images, self.H, self.W, self.patch_size,
                    self.n_patches, self.same_image, self.corner_mode, out["img_idxs"], out["pix_idxs"])
         rays_o, rays_d, rgb = self._rays(out["img_idxs"], out["pix_idxs"], out)
-        return {"rays_o": rays_o, "rays_d": rays_d, "rgb": rgb, "img_idxs": out["img_idxs"],
-                "pix_idxs": out["pix_idxs"], "patch_area": self.patch_size * self.patch_size,
-                "x1_offsets_local": self.x1_off, "x2_offsets_local": self.x2_off, "x3_offsets_local": self.x3_off}
+        batch = {"rays_o": rays_o, "rays_d": rays_d, "rgb": rgb, "img_idxs": out["img_idxs"],
+                 "pix_idxs": out["pix_idxs"], "patch_area": self.patch_size * self.patch_size,
+                 "x1_offsets_local": self.x1_off, "x2_offsets_local": self.x2_off, "x3_offsets_local": self.x3_off}
+        if self.planes:  # (one launch for all of them)
+            batch_labels_fw(out["img_idxs"], out["pix_idxs"], self.planes, out)
+            batch.update((k, out[k]) for k in self.planes)
+        return batch
 
     def image_rays(self, v):
         """Every pixel of view v — rays_o, rays_d, rgb (H*W, 3) — through the same forward kernel (with
@@ -177,7 +220,7 @@ class DeviceRayDataset:
         if not 0 <= int(v) < self.n_images:
             raise IndexError(f"view {v} of {self.n_images}")
         n = self.H * self.W
-        out = self.buffers(n)
+        out = self.buffers(n, labels=False)
         out["img_idxs"].fill_(int(v))
         torch.arange(n, out=out["pix_idxs"])
         with torch.no_grad():

@@ -15,6 +15,15 @@ rounds with spherical renormalisation and faiss's split_clusters for empty clust
 RandomGenerator walk from a host-built std::mt19937 plan), then a final search over all points.
 faiss itself is not available here: parity unpinned w.r.t. faiss, see DESIGN.md §3.
 
+The geometry supervision — depth L2, the two GT-normal terms and RegNeRF — is one autograd node
+(`_GeomLoss`) over two entry points, `ncn_geom_loss_fwd` / `ncn_geom_loss_bwd` (include/ncnerf_geom.h):
+masks, fixed-order sums, the validity filter and the RegNeRF step gate all stay on the device, so
+these terms run inside a captured step (a device `global_step`) like the rest.  The normal terms'
+gradient is carried through the triangle normals to the depth inside the backward launch, which
+skips every triangle of a filtered term: the reference replaces such a term by a constant, so no
+0 * NaN of a NaN depth may reach the gradient.  Only under pose refinement (the rays require grad)
+does it go on as dL/dnormals into `_Normals.backward`, which also reaches the rays.
+
 Pose refinement (train_nerf.py --optimize_ext: the prediction's rays require grad): `_Normals`
 back-propagates into rays_o / rays_d (`ncn_normals_bwd_rays`), NeRFMTLoss.forward then takes the
 unfused `_Normals` + `cluster_losses` branch, and the fused nodes, which stop at the depth, raise.
@@ -173,6 +182,122 @@ def cluster_losses(norm_depth, K=K_CLUSTERS, niter=K_ITERS, seed=1234, t_similar
     """Weighted (ort, centr_dot, centr_L1) terms, labels (+-1..3, 0, -9 invalid), centroids, raw stats."""
     check_input(norm_depth, "norm_depth")
     return _ClusterLoss.apply(norm_depth, K, niter, seed, t_similar, _weights_arg(w))
+
+
+GEOM_DEPTH, GEOM_NORM_L1, GEOM_NORM_DOT, GEOM_REG = 1, 2, 4, 8  # NCN_GEOM_* (include/ncnerf_geom.h)
+GEOM_KEYS = ("depth", "norm_D_L1", "norm_D_dot", "reg_depth")  # the node's four terms, in its order
+
+
+def geom_workspace_doubles(n_rays, n_tri):
+    """ncn_geom_loss_fwd's workspace: 6 * G(max(n_rays, n_tri, 1)), G(n) = min(ceil(n / 256), 1024)."""
+    return 6 * min(-(-max(n_rays, n_tri, 1) // 256), 1024)
+
+
+class _GeomLoss(torch.autograd.Function):
+    """losses.py:372-417 on the GPU: the depth, GT-normal L1 / dot and RegNeRF terms of `terms` in one
+    forward and one backward entry point (at most two kernels each, ncnerf_geom.h).  Returns the four weighted terms after the validity
+    filter (0-d, differentiable; 0 for a term that is off or filtered) and, as non-differentiable
+    extras, the kernel's row (8: the terms, their raw sums) and counts (8: mask sizes, live flags).
+    rays (rays_o, rays_d) or None: with them `normals` is taken as ncn_normals_fwd of (rays, depth,
+    triangles) and not differentiated itself: the normal terms' gradient arrives in dL/ddepth."""
+
+    @staticmethod
+    def forward(ctx, depth, normals, depth_gt, normals_gt, x1, x2, x3, terms, w, step_dev, step, reg_start, rays):
+        R, T = depth.shape[0], (0 if x1 is None else x1.shape[0])
+        dev = depth.device
+        ws = torch.empty(geom_workspace_doubles(R, T), dtype=torch.float64, device=dev)
+        out = torch.empty(8, dtype=torch.float32, device=dev)
+        counts = torch.empty(8, dtype=torch.int64, device=dev)
+        call("ncn_geom_loss_fwd", depth, depth_gt, R, normals, normals_gt, x1, x2, x3, T, terms, w[0], w[1], w[2],
+             step_dev, step, reg_start, ws, ws.numel(), out, counts)
+        ro, rd = rays if rays is not None else (None, None)
+        ctx.save_for_backward(depth, normals, depth_gt, normals_gt, x1, x2, x3, counts, ro, rd)
+        ctx.terms, ctx.w = terms, w
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(out, counts)
+        return out[0], out[1], out[2], out[3], out, counts
+
+    @staticmethod
+    def backward(ctx, g_depth, g_l1, g_dot, g_reg, _g_out, _g_counts):
+        depth, normals, depth_gt, normals_gt, x1, x2, x3, counts, ro, rd = ctx.saved_tensors
+        gs = (g_depth, g_l1, g_dot, g_reg)
+        none = (None,) * 13
+        if all(g is None for g in gs):
+            return none
+        z = torch.zeros((), dtype=torch.float32, device=depth.device)
+        up = torch.stack([z if g is None else g.float().reshape(()) for g in gs])
+        ddepth = torch.empty_like(depth) if ctx.needs_input_grad[0] else None
+        dn = torch.empty_like(normals) if normals is not None and ro is None and ctx.needs_input_grad[1] else None
+        if ddepth is None and dn is None:
+            return none
+        call("ncn_geom_loss_bwd", depth, depth_gt, depth.shape[0], normals, normals_gt, x1, x2, x3,
+             0 if x1 is None else x1.shape[0], ro, rd, ctx.terms, ctx.w[0], ctx.w[1], ctx.w[2], counts, up, ddepth, dn)
+        return (ddepth, dn) + none[2:]
+
+
+def geometry_losses(depth, x123_idx=None, depth_gt=None, normals=None, normals_gt=None, terms=0, w=(1.0, 1.0, 1.0),
+                    step=0, reg_start=0, rays=None):
+    """The geometry terms of `terms` (GEOM_* bits) on depth (R): depth L2 against depth_gt (R) over
+    depth_gt > 0; L1 / (1 - cos) of normals (T, 3) against normals_gt[x1] over its non-zero rows,
+    normals_gt (R, 3); RegNeRF over the triangles x123_idx while step > reg_start.  w: the weights of
+    the first three terms; step: an int, or a device int64 scalar (read by the kernel: no host read).
+    rays = (rays_o, rays_d) (R, 3): `normals` are extract_normals_from_ray_batch of these rays, the
+    depth and the triangles, and the normal terms back-propagate to the depth through them inside the
+    node (normals itself gets no gradient); without rays they back-propagate to `normals`.
+    -> ((depth, norm_D_L1, norm_D_dot, reg_depth) 0-d tensors, row (8) f32, counts (8) int64)."""
+    f = lambda t: None if t is None else t.float().contiguous()
+    terms = int(terms)
+    if not 0 <= terms < 16:
+        raise ValueError(f"terms {terms}: a sum of GEOM_DEPTH, GEOM_NORM_L1, GEOM_NORM_DOT, GEOM_REG")
+    need_norm, need_tri = terms & (GEOM_NORM_L1 | GEOM_NORM_DOT), terms & (GEOM_NORM_L1 | GEOM_NORM_DOT | GEOM_REG)
+    given = [(depth, "depth")]
+    given += [(depth_gt, "depth_gt")] if terms & GEOM_DEPTH else []
+    given += [(normals, "normals"), (normals_gt, "normals_gt")] if need_norm else []
+    for t, n in given:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{n} must be a CUDA tensor")
+    R = depth.shape[0]
+    if depth.dim() != 1:
+        raise ValueError(f"depth must be (R) (got {tuple(depth.shape)})")
+    x1 = x2 = x3 = None
+    if need_tri:
+        if x123_idx is None:
+            raise ValueError("the normal and RegNeRF terms need the triangles x123_idx")
+        x1, x2, x3 = (x123_idx[k].long().contiguous() for k in ("x1", "x2", "x3"))
+        for x in (x1, x2, x3):
+            check_input(x, "x123_idx")
+        if not (x1.shape == x2.shape == x3.shape and x1.dim() == 1):
+            raise ValueError("x123_idx: x1, x2 and x3 must be (T) each")
+    if terms & GEOM_DEPTH:
+        if depth_gt.numel() != R:
+            raise ValueError(f"depth_gt must cover the {R} rays of depth (got {tuple(depth_gt.shape)})")
+        depth_gt = f(depth_gt).reshape(-1)
+    else:
+        depth_gt = None
+    if need_norm:
+        if tuple(normals.shape) != (x1.shape[0], 3):
+            raise ValueError(f"normals must be ({x1.shape[0]}, 3) (got {tuple(normals.shape)})")
+        if tuple(normals_gt.shape) != (R, 3):
+            raise ValueError(f"normals_gt must be ({R}, 3) (got {tuple(normals_gt.shape)})")
+        normals, normals_gt = f(normals), f(normals_gt)
+        if rays is not None:
+            for t, n in zip(rays, ("rays_o", "rays_d")):
+                if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                    raise RuntimeError(f"{n} must be a CUDA tensor")
+                if tuple(t.shape) != (R, 3):
+                    raise ValueError(f"{n} must be ({R}, 3) (got {tuple(t.shape)})")
+            rays, normals = (f(rays[0]).detach(), f(rays[1]).detach()), normals.detach()
+    else:
+        normals = normals_gt = rays = None
+    if isinstance(step, torch.Tensor):
+        if not step.is_cuda:
+            raise RuntimeError("step must be an int or a CUDA tensor")
+        step_dev, step = step.to(torch.int64).reshape(()).contiguous(), 0
+    else:
+        step_dev, step = None, int(step)
+    res = _GeomLoss.apply(f(depth), normals, depth_gt, normals_gt, x1, x2, x3, terms, tuple(float(x) for x in w),
+                          step_dev, step, int(reg_start), rays)
+    return res[:4], res[4], res[5]
 
 
 def _no_ray_grad(rays_need_grad, who):
@@ -376,8 +501,6 @@ class NeRFMTLoss(nn.Module):
         grow = h.get("loss_norm_can_grow", 1)
         self.w_sched = lambda w, step: max(0, min(w, (step - start) * (w / grow)))  # losses.py:217
         self._grow = grow
-        self.L1_norm = lambda x, y: ((torch.abs(x - y)).sum(-1)).mean()
-        self.dot_prod = lambda x, y: (1.0 - torch.nn.CosineSimilarity(dim=-1)(x, y)).mean()
         if self.pred_norm_depth:
             assert self.ray_sampling_strategy in ["all_images_triang", "all_images_triang_val", "same_image_triang",
                                                   "all_images_triang_patch", "same_image_triang_patch"]
@@ -423,6 +546,39 @@ class NeRFMTLoss(nn.Module):
                     self._idx_cache.clear()
                 self._idx_cache[key] = hit
         return hit
+
+    def _geometry(self, pred_w_gt, pred_unsup, target_gt, step, shared, rays_grad):
+        """losses.py:372-417: the depth, GT-normal and RegNeRF terms that are switched on, through
+        `geometry_losses` (no host read).  shared: the supervised rays are the unsupervised ones
+        (no random_tr_poses), so one node serves all four terms; otherwise the RegNeRF term, which
+        runs on the unsupervised rays, is a node of its own.  With a host step the RegNeRF entry is
+        absent until step > loss_norm_can_start, as in the reference; with a device step it is
+        always there and 0 until then.  rays_grad (pose refinement): the normal terms back-propagate
+        into the `_Normals` node, which reaches the rays; otherwise inside the geometry node."""
+        sup = (GEOM_DEPTH if self.depth_w > 0 else 0) | (GEOM_NORM_L1 if self.norm_DEpth_L1_w > 0 else 0) | (
+            GEOM_NORM_DOT if self.norm_DEpth_dot_w > 0 else 0)
+        reg = GEOM_REG if self.reg_depth_w > 0 and (isinstance(step, torch.Tensor) or step > self.can_sched_start) else 0
+        if sup & (GEOM_NORM_L1 | GEOM_NORM_DOT) and "norm_depth" not in pred_w_gt:
+            raise ValueError("loss_norm_depth_L1_w / loss_norm_depth_dot_w need pred_norm_depth and a triangle "
+                             "ray_sampling_strategy")
+        if reg and "x123_idx" not in pred_unsup:
+            raise ValueError("loss_reg_depth_w needs a triangle ray_sampling_strategy")
+        w = (self.depth_w, self.norm_DEpth_L1_w, self.norm_DEpth_dot_w)
+        jobs = [(sup | reg, pred_w_gt)] if shared else [(sup, pred_w_gt), (reg, pred_unsup)]
+        loss_d = {}
+        for terms, pred in jobs:
+            if not terms:
+                continue
+            norm = terms & (GEOM_NORM_L1 | GEOM_NORM_DOT)
+            vals, _row, _counts = geometry_losses(
+                pred["depth"], pred.get("x123_idx"), target_gt.get("depth") if terms & GEOM_DEPTH else None,
+                pred["norm_depth"] if norm else None, target_gt[self.norm_GT] if norm else None, terms, w,
+                0 if step is None else step, self.can_sched_start,
+                None if rays_grad or not norm else (pred["rays_o"], pred["rays_d"]))
+            for bit, key, v in zip((GEOM_DEPTH, GEOM_NORM_L1, GEOM_NORM_DOT, GEOM_REG), GEOM_KEYS, vals):
+                if terms & bit:
+                    loss_d[key] = v
+        return loss_d
 
     def _fused(self, pred_w_gt, target_gt, pred_unsup, kwargs):
         """The reference configuration in one autograd node (_NeRFLossFused)."""
@@ -521,27 +677,12 @@ class NeRFMTLoss(nn.Module):
             ts = pred_raw["ts"].float().contiguous()
             dist = DistortionLoss.apply(ts, pred_raw["deltas"].float().contiguous(), ts, pred_raw["rays_a"].contiguous())
             loss_d["distortion"] = self._validity(self.distortion_w * dist.mean(), dev)
-        if self.depth_w > 0:
-            d_pred, d_tgt = pred_w_gt["depth"], target_gt["depth"]
-            valid = d_tgt > 0
-            loss_d["depth"] = self._validity(self.depth_w * ((d_pred[valid] - d_tgt[valid]) ** 2).mean(), dev)
-        if self.norm_DEpth_L1_w > 0 or self.norm_DEpth_dot_w > 0:
-            nd = pred_w_gt["norm_depth"]
-            tgt = target_gt[self.norm_GT][pred_w_gt["x123_idx"]["x1"]]
-            valid = tgt.abs().sum(-1) > 0
-            if self.norm_DEpth_L1_w > 0:
-                loss_d["norm_D_L1"] = self._validity(self.norm_DEpth_L1_w * self.L1_norm(nd[valid], tgt[valid]), dev)
-            if self.norm_DEpth_dot_w > 0:
-                loss_d["norm_D_dot"] = self._validity(self.norm_DEpth_dot_w * self.dot_prod(nd[valid], tgt[valid]),
-                                                      dev)
         step_t = isinstance(kwargs.get("global_step"), torch.Tensor)
-        if step_t and (self.reg_depth_w > 0 or self.can_sched_end != -1):
+        if step_t and self.can_sched_end != -1:
             raise NotImplementedError("a device global_step needs step-independent control flow "
-                                      "(loss_reg_depth_w == 0 and loss_norm_can_end == -1)")
-        if self.reg_depth_w > 0 and kwargs["global_step"] > self.can_sched_start:
-            d_pred, x = pred_unsup["depth"], pred_unsup["x123_idx"]
-            reg = ((d_pred[x["x1"]] - d_pred[x["x2"]]) ** 2 + (d_pred[x["x1"]] - d_pred[x["x3"]]) ** 2).mean()
-            loss_d["reg_depth"] = self._validity(reg, dev)
+                                      "(loss_norm_can_end == -1)")
+        loss_d.update(self._geometry(pred_w_gt, pred_unsup, target_gt, kwargs.get("global_step"), unsup_start == 0,
+                                     rays_grad))
         if clustering:
             step = kwargs["global_step"]
             if step_t or step <= self.can_sched_end or self.can_sched_end == -1:
