@@ -4,6 +4,7 @@
 #pragma once
 #include "cluster_lloyd.h"
 #include "cluster_select.h"
+#include "workgroup.h"
 
 namespace ncn {
 
@@ -293,7 +294,7 @@ __device__ __forceinline__ void cluster_body(
             v[e] = q < R * NW ? (&L.wcnt[0][0])[q] : 0;
             sacc += v[e];
         }
-        const int incl = wave_incl_sum_i(sacc, lane);
+        const int incl = wave_incl_sum(sacc, lane);
         int run = incl - sacc;
 #pragma unroll
         for (int e = 0; e < 4; e++) {

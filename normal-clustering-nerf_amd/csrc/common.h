@@ -22,39 +22,6 @@ __device__ __forceinline__ float shfl(float v, int src) {
 }
 __device__ __forceinline__ int shfl_i(int v, int src) { return __builtin_amdgcn_ds_bpermute(src << 2, v); }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// Inclusive scans across the 64 lanes (Hillis-Steele, 6 steps).
-__device__ __forceinline__ int wave_incl_sum_i(int v, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(v, off, 64);
-        if (lane >= off) v += o;
-    }
-    return v;
-}
-
-__device__ __forceinline__ float wave_incl_sum(float v, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        float o = __shfl_up(v, off, 64);
-        if (lane >= off) v += o;
-    }
-    return v;
-}
-__device__ __forceinline__ float wave_incl_prod(float v, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        float o = __shfl_up(v, off, 64);
-        if (lane >= off) v *= o;
-    }
-    return v;
-}
-
 // DPP wave scans (GFX9 DPP: row_shr within 16-lane rows, then row_bcast:15 / row_bcast:31 across
 // rows): 6 DPP ops with ~no latency, no LDS crossbar traffic (unlike __shfl_* = ds_bpermute).
 template <int CTRL, int ROW_MASK>
@@ -210,33 +177,6 @@ __device__ __forceinline__ int opaque_zero() {
 // gather the same hash-table entries — inside one L2.  Identity when G is not a multiple of 8.
 // (Placement is a performance hint only: nothing may depend on it for correctness.)
 __device__ __forceinline__ int xcd_block(int b, int G) { return (G & 7) ? b : (b & 7) * (G >> 3) + (b >> 3); }
-
-// total_samples.sum() by one 1024-thread workgroup (+ optional f64 accumulators: acc[0] +=
-// counter[0] (marched), acc[1] += the sum (composited)) — ncn_count_samples, and the extra
-// workgroup of ncn_photo_normals_count_fwd.
-__device__ __forceinline__ void count_samples_wg(const int64_t* __restrict__ total, int64_t R,
-                                                 const int32_t* __restrict__ counter, int64_t* __restrict__ sum_out,
-                                                 double* __restrict__ acc) {
-    __shared__ long long part[16];
-    long long v = 0;
-    for (int64_t i = threadIdx.x; i < R; i += blockDim.x) v += total[i];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)v, off, 64), hi = __shfl_xor((unsigned)((unsigned long long)v >> 32), off, 64);
-        v += (long long)(((unsigned long long)hi << 32) | lo);
-    }
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long t = 0;
-        for (int w = 0; w < (int)(blockDim.x >> 6); w++) t += part[w];
-        *sum_out = t;
-        if (acc) {
-            acc[0] += counter ? (double)counter[0] : 0.0;
-            acc[1] += (double)t;
-        }
-    }
-}
 
 // Workgroup barrier that orders LDS only: waits for the wave's own LDS operations (lgkmcnt) but
 // not for its outstanding global loads/stores/atomics (vmcnt), which __syncthreads() also drains.

@@ -8,7 +8,7 @@
 // All three read no host value but their arguments, allocate nothing and never synchronise, so they
 // can be nodes of a captured step.  An index outside its range (img_idxs / pix_idxs filled by a
 // caller) gives NaN outputs, never an out-of-bounds access.
-#include "common.h"
+#include "workgroup.h"
 #include "../../include/ncnerf.h"
 
 #include <math.h>
@@ -194,6 +194,9 @@ __global__ __launch_bounds__(BW_THREADS) void batch_rays_bw_kernel(
             acc[9 + i] += g_o[3 * r + i];
         }
     }
+    // (block_sum<12>'s order, written out: through block_sum the outputs came out with other bits
+    // (profiles/workgroup/ab_outputs.txt) although the sums' order is the same — thread 0's tail below
+    // then compiles differently; how its a * b + c * d sums are contracted is the suspect, unproven)
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < 12; k++) {

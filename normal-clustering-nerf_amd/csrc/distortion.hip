@@ -5,7 +5,7 @@
 // One wave per ray, the segment in rows of 64 samples; each row's prefix sums are a DPP wave scan
 // plus the carry of the previous rows (the reference scans serially with thrust: fp32 rounding
 // order differs, tolerance in tests/test_gpu_distortion.py).
-#include "common.h"
+#include "workgroup.h"
 #include "../../include/ncnerf.h"
 
 namespace ncn {

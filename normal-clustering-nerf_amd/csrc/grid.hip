@@ -21,7 +21,7 @@
 #pragma clang fp contract(off)
 
 #include <algorithm>
-#include "common.h"
+#include "workgroup.h"
 #include "../../include/ncnerf.h"
 
 namespace ncn {
@@ -71,45 +71,14 @@ __device__ __forceinline__ float cell_decay(float decay, const float* __restrict
     return fminf(fmaxf(powf(decay, 1.0f / count[i]), 0.1f), 0.95f);
 }
 
-// Agent-scope hand-off of per-workgroup partials to the last workgroup to arrive
-// (MI355X_MICROARCH.md, inter-workgroup visibility): store, wait, one arrival add.
-template <typename T>
-__device__ __forceinline__ bool gr_arrive(T* slot, T v, unsigned* arrive) {
-    __shared__ bool last;
-    if (threadIdx.x == 0) {
-        __hip_atomic_store(slot, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        last = __hip_atomic_fetch_add(arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-    }
-    __syncthreads();
-    return last;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)v, off, 64), hi = __shfl_xor((unsigned)(v >> 32), off, 64);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // Sum of the gridDim.x (<= 256) published partials by the 256 threads of the last workgroup: one
 // agent-scope load per thread (a single round trip), wave sums, then 4 values through LDS.
 template <typename T>
-__device__ __forceinline__ T gr_final_sum(const T* part, T (*wsum)(T)) {
+__device__ __forceinline__ T gr_final_sum(const T* part) {
     __shared__ T red[4];
-    T v = threadIdx.x < gridDim.x ? __hip_atomic_load(&part[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                  : (T)0;
-    v = wsum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
+    const T v = threadIdx.x < gridDim.x ? __hip_atomic_load(&part[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                                        : (T)0;
+    return block_sum<256>(v, red);
 }
 
 // 1. cells of the cascade with density > threshold (`torch.nonzero(grid[c] > thr)`, ngp_mt.py:256)
@@ -129,11 +98,8 @@ __global__ __launch_bounds__(256) void grid_occ_kernel(const float* __restrict__
         for (int u = 0; u < GR_UNROLL; u++)
             c += (x[u].x > thr) + (x[u].y > thr) + (x[u].z > thr) + (x[u].w > thr);
     }
-    c = wave_sum_u64(c);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (!gr_arrive(&w->pcnt[blockIdx.x], red[0] + red[1] + red[2] + red[3], &w->arrive)) return;
-    const unsigned long long t = gr_final_sum<unsigned long long>(w->pcnt, wave_sum_u64);
+    if (!last_block_arrive(&w->pcnt[blockIdx.x], block_sum<256>(c, red), &w->arrive)) return;
+    const unsigned long long t = gr_final_sum(w->pcnt);
     if (threadIdx.x == 0) {
         const double p = t > 0 ? -expm1((double)M * log1p(-1.0 / (double)t)) : 0.0;
         w->p_occ = (float)p;
@@ -179,7 +145,7 @@ __global__ __launch_bounds__(256) void grid_select_kernel(float* __restrict__ gr
     static_assert(GS_ITER * 4 <= 64, "one count per lane");
     if (threadIdx.x < 64) {  // exclusive scan of the GS_ITER*4 counts in (round, wave) order, one per lane
         const int c0 = lane < GS_ITER * 4 ? (&cnt[0][0])[lane] : 0;
-        const int incl = wave_incl_sum_i(c0, lane);
+        const int incl = wave_incl_sum(c0, lane);
         const int total = __shfl(incl, 63, 64);
         int base = 0;
         if (lane == 63 && total > 0) base = atomicAdd(n_list, total);
@@ -246,22 +212,16 @@ __global__ __launch_bounds__(256) void grid_mean_kernel(const float* __restrict_
                 if (e[q] > 0.f) { s += (double)e[q]; c++; }
         }
     }
-    s = wave_sum_f64(s);
-    c = wave_sum_u64(c);
-    if ((threadIdx.x & 63) == 0) { rs[threadIdx.x >> 6] = s; rc[threadIdx.x >> 6] = c; }
-    __syncthreads();
-    if (threadIdx.x == 0)
-        __hip_atomic_store(&w->psum[blockIdx.x], rs[0] + rs[1] + rs[2] + rs[3], __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    if (!gr_arrive(&w->pcnt[blockIdx.x], rc[0] + rc[1] + rc[2] + rc[3], &w->arrive)) return;
-    const double ts = gr_final_sum<double>(w->psum, wave_sum_f64);
-    const unsigned long long tc = gr_final_sum<unsigned long long>(w->pcnt, wave_sum_u64);
-    {
-        if (threadIdx.x == 0) {
-            const float mean = tc > 0 ? (float)(ts / (double)tc) : __int_as_float(0x7fc00000);
-            *thr_out = thr < (double)mean ? (float)thr : mean;  // Python min(mean, thr)
-            w->arrive = 0;
-        }
+    s = block_sum<256>(s, rs);
+    c = block_sum<256>(c, rc);
+    if (threadIdx.x == 0) __hip_atomic_store(&w->psum[blockIdx.x], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!last_block_arrive(&w->pcnt[blockIdx.x], c, &w->arrive)) return;
+    const double ts = gr_final_sum(w->psum);
+    const unsigned long long tc = gr_final_sum(w->pcnt);
+    if (threadIdx.x == 0) {
+        const float mean = tc > 0 ? (float)(ts / (double)tc) : __int_as_float(0x7fc00000);
+        *thr_out = thr < (double)mean ? (float)thr : mean;  // Python min(mean, thr)
+        w->arrive = 0;
     }
 }
 

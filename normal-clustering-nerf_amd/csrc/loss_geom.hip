@@ -3,7 +3,7 @@
 // from device-resident planes — behind the C ABI of include/ncnerf_geom.h.
 //  * ncn_geom_loss_fwd    one streaming pass over rays and triangles for every term that is on, its
 //                         workgroups' partial sums into the workspace, then one workgroup (the
-//                         fixed-order reduction of metrics_reduce.h: doubles, no float atomics)
+//                         fixed-order reduction of workgroup.h: doubles, no float atomics)
 //  * ncn_geom_loss_bwd    dL/ddepth (one thread per ray, plain stores) and dL/dnormals (one thread
 //                         per triangle) in one pass; the triangle-to-ray scatter on top: the RegNeRF
 //                         term and, given the rays, the normal terms through loss_normals.h's
@@ -16,9 +16,8 @@
 
 #include <algorithm>
 #include <cmath>
-#include "common.h"
 #include "loss_normals.h"
-#include "metrics_reduce.h"
+#include "workgroup.h"
 #include "../../include/ncnerf_geom.h"
 
 namespace ncn {

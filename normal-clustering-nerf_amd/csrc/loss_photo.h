@@ -2,6 +2,7 @@
 // sample count in one launch) and backward, and the fused backward of the reference configuration.
 #pragma once
 #include "loss_normals.h"
+#include "workgroup.h"
 
 namespace ncn {
 
@@ -11,25 +12,20 @@ constexpr int PH_THREADS = 1024;
 __device__ __forceinline__ void photo_loss_fwd_wg(const float* __restrict__ rgb, const float* __restrict__ gt,
                                                   const float* __restrict__ op, int64_t R, float w_op,
                                                   float* __restrict__ loss) {
-    __shared__ float red[2][PH_THREADS / 64];
-    float a = 0.f, b = 0.f;
+    __shared__ float red[PH_THREADS / 64][2];
+    float s[2] = {0.f, 0.f};  // (accumulators that start at +0 are never -0: the sums need no 0 in front)
     for (int64_t i = threadIdx.x; i < R; i += PH_THREADS) {
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             const float d = rgb[3 * i + c] - gt[3 * i + c];
-            a += d * d;
+            s[0] += d * d;
         }
         const float o = op[i] + 1e-10f;
-        b += -o * logf(o);
+        s[1] += -o * logf(o);
     }
-    a = wave_sum(a);
-    b = wave_sum(b);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = b; }
-    __syncthreads();
+    block_sum<2, PH_THREADS>(s, red);
     if (threadIdx.x == 0) {
-        float sa = 0.f, sb = 0.f;
-        for (int w = 0; w < PH_THREADS / 64; w++) { sa += red[0][w]; sb += red[1][w]; }
-        const float mse = sa / (float)(3 * R), ent = w_op * (sb / (float)R);
+        const float mse = s[0] / (float)(3 * R), ent = w_op * (s[1] / (float)R);
         loss[0] = isfinite(mse) ? mse : 0.f;  // validity filter
         loss[1] = isfinite(ent) ? ent : 0.f;
         loss[2] = isfinite(mse) ? 1.f : 0.f;

@@ -17,7 +17,7 @@
 #pragma clang fp contract(off)
 
 #include <cmath>
-#include "common.h"
+#include "workgroup.h"
 #include "vren_march.h"
 #include "../../include/ncnerf_mesh.h"
 
@@ -261,16 +261,8 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_scan_local_kernel(const uin
             sum += (c >> (8 * r)) & 0xFF;
         }
     }
-    const int lane = lane_id(), wave = threadIdx.x / WAVE;
-    const int incl = wave_incl_sum_i(sum, lane);
-    if (lane == WAVE - 1) wave_total[wave] = incl;
-    __syncthreads();
-    int before = incl - sum, total = 0;
-#pragma unroll
-    for (int q = 0; q < MESH_THREADS / WAVE; q++) {
-        if (q < wave) before += wave_total[q];
-        total += wave_total[q];
-    }
+    int total;
+    const int before = block_excl_scan<MESH_THREADS>(sum, total, wave_total);
     if (full) {
         uint32_t o[8];
 #pragma unroll
@@ -289,27 +281,12 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_scan_local_kernel(const uin
 __global__ __launch_bounds__(NCN_MESH_SCAN_SWEEP) void mesh_scan_base_kernel(int64_t* __restrict__ block_base, int64_t nb,
                                                                              int64_t* __restrict__ total) {
     __shared__ long long wave_total[NCN_MESH_SCAN_SWEEP / WAVE];
-    const int lane = lane_id(), wave = threadIdx.x / WAVE;
     long long carry = 0;
     for (int64_t s0 = 0; s0 < nb; s0 += NCN_MESH_SCAN_SWEEP) {  // (uniform trip count: the barriers are safe)
         const int64_t i = s0 + threadIdx.x;
         const long long own = i < nb ? (long long)block_base[i] : 0;
-        long long incl = own;
-#pragma unroll
-        for (int off = 1; off < WAVE; off <<= 1) {
-            const long long o = __shfl_up(incl, off, WAVE);
-            if (lane >= off) incl += o;
-        }
-        if (lane == WAVE - 1) wave_total[wave] = incl;
-        __syncthreads();
-        long long before = carry, sweep = 0;
-        for (int q = 0; q < NCN_MESH_SCAN_SWEEP / WAVE; q++) {
-            if (q < wave) before += wave_total[q];
-            sweep += wave_total[q];
-        }
-        if (i < nb) block_base[i] = (int64_t)(before + incl - own);
-        carry += sweep;
-        __syncthreads();
+        const long long before = block_excl_sweep<NCN_MESH_SCAN_SWEEP>(own, carry, wave_total);
+        if (i < nb) block_base[i] = (int64_t)before;
     }
     if (threadIdx.x == 0) total[0] = (int64_t)carry;
 }

@@ -10,8 +10,7 @@
 
 #include <algorithm>
 #include <cmath>
-#include "common.h"
-#include "metrics_reduce.h"
+#include "workgroup.h"
 #include "metrics_ssim.h"
 #include "metrics_select.h"
 #include "../../include/ncnerf_metrics.h"

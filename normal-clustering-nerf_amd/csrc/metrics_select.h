@@ -8,7 +8,7 @@
 // free; the prefix is not stored anywhere: every workgroup re-derives it from the earlier passes'
 // histograms (a 256-thread scan of at most 2048 counters from L2).  The host never reads n or k.
 #pragma once
-#include "common.h"
+#include "workgroup.h"
 
 namespace ncn {
 
@@ -34,7 +34,7 @@ __device__ __forceinline__ bool sel_find(const uint32_t* __restrict__ hist, int 
         c[i] = i < per ? (int)hist[t * per + i] : 0;
         s += c[i];
     }
-    int incl = wave_incl_sum_i(s, lane);
+    int incl = wave_incl_sum(s, lane);
     __syncthreads();  // tmp may still be read from an earlier call
     if (lane == WAVE - 1) tmp[t / WAVE] = incl;
     if (t == 0) tmp[6] = 0;

@@ -16,8 +16,7 @@
 // and covariances are shift invariant, so each thread subtracts the value of ITS column element at
 // the tile's middle row from everything it reads; mu gets the shift back.
 #pragma once
-#include "common.h"
-#include "metrics_reduce.h"
+#include "workgroup.h"
 
 namespace ncn {
 

@@ -3,7 +3,7 @@
 // 0.05, train_nerf.py:955 via PL -> torch.nn.utils.clip_grad_norm_).  The clip factor is computed
 // on device from the sum-of-squares partials, so the step has no host synchronisation.
 #include <algorithm>
-#include "common.h"
+#include "workgroup.h"
 #include "../../include/ncnerf.h"
 
 namespace ncn {
@@ -23,10 +23,8 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x,
     }
     if (blockIdx.x == 0)
         for (int64_t i = n4 * 4 + threadIdx.x; i < n; i += 256) s = fmaf(x[i], x[i], s);
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+    s = block_sum<256>(s, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
 __device__ __forceinline__ float clip_coef(const float* __restrict__ part, float max_norm) {
@@ -110,9 +108,7 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_prep_kernel(const float* __
     float* part = work;                                // [ADAM_BLOCKS]
     unsigned* cnt = (unsigned*)(work + ADAM_BLOCKS);   // arrival counter (left zero)
     float* sc = work + ADAM_BLOCKS + 4;                // cf, bc1, bc2, lr, skip (AMP)
-    constexpr int NW = ADAM_THREADS / 64;
-    __shared__ float red[NW];
-    __shared__ bool last;
+    __shared__ float red[ADAM_THREADS / 64];
     const int64_t n4 = n / 4, stride = (int64_t)gridDim.x * ADAM_THREADS;
     const float4* g4 = (const float4*)g;
     float s = 0.f;
@@ -127,26 +123,8 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_prep_kernel(const float* __
     }
     if (blockIdx.x == 0)
         for (int64_t i = 4 * n4 + threadIdx.x; i < n; i += ADAM_THREADS) s = fmaf(g[i], g[i], s);
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    // Hand-off in the sc1 form of MI355X_MICROARCH.md "Correctness boundaries" (inter-workgroup
-    // visibility): the partial is stored with an agent-scope (sc1) store and drained (vmcnt(0))
-    // before the arrival add, and the last workgroup reads the partials with agent-scope (sc1)
-    // loads.  This relies on gfx9's in-order completion of one wave's vector memory operations
-    // after vmcnt(0), not on a HIP release/acquire pair: an agent-scope release fence writes back
-    // the whole L2 (buffer_wbl2), which right after the table-gradient scatter measured ~40 us.
-    // (The asm's "memory" clobber keeps the compiler from moving the store past the add.)
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; w++) t += red[w];
-        __hip_atomic_store(&part[blockIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        last = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!last) return;
+    // (s >= +0: a sum of squares onto +0 is never -0, so the waves' totals need no 0 in front)
+    if (!last_block_arrive(&part[blockIdx.x], block_sum<ADAM_THREADS>(s, red), cnt)) return;
     // the gridDim.x (<= ADAM_BLOCKS) partials, fixed-order sum in wave 0
     if (threadIdx.x < 64) {
         float q[ADAM_BLOCKS / 64];

@@ -2,6 +2,7 @@
 // place (the second launch of the fused marcher).
 #pragma once
 #include "vren_march_wave.h"
+#include "workgroup.h"
 
 namespace ncn {
 
@@ -11,11 +12,9 @@ __global__ __launch_bounds__(1024) void march_train_scan_kernel(const int32_t* _
                                                                 int64_t* __restrict__ rays_a,
                                                                 int32_t* __restrict__ counter) {
     __shared__ int wave_tot[16];
-    __shared__ int carry_s;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    if (tid == 0) carry_s = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < R; base += 4096) {
+    const int tid = threadIdx.x;
+    int carry = 0;
+    for (int64_t base = 0; base < R; base += 4096) {  // (uniform trip count: the barriers are safe)
         const int64_t i0 = base + (int64_t)tid * 4;
         int c[4];
         int local = 0;
@@ -24,21 +23,7 @@ __global__ __launch_bounds__(1024) void march_train_scan_kernel(const int32_t* _
             c[j] = (i0 + j < R) ? counts[i0 + j] : 0;
             local += c[j];
         }
-        int incl = local;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            int o = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += o;
-        }
-        if (lane == 63) wave_tot[wid] = incl;
-        __syncthreads();
-        int wave_off = 0, block_tot = 0;
-        for (int w = 0; w < 16; w++) {
-            if (w < wid) wave_off += wave_tot[w];
-            block_tot += wave_tot[w];
-        }
-        const int carry = carry_s;
-        int run = carry + wave_off + incl - local;
+        int run = block_excl_sweep<1024>(local, carry, wave_tot);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int64_t i = i0 + j;
@@ -49,12 +34,9 @@ __global__ __launch_bounds__(1024) void march_train_scan_kernel(const int32_t* _
             }
             run += c[j];
         }
-        __syncthreads();
-        if (tid == 0) carry_s = carry + block_tot;
-        __syncthreads();
     }
     if (tid == 0) {
-        counter[0] = carry_s;
+        counter[0] = carry;
         counter[1] = (int32_t)R;
     }
 }
@@ -98,7 +80,7 @@ __global__ __launch_bounds__(256) void march_train_place_kernel(
     const int32_t* __restrict__ wg_sum, const float* __restrict__ slab_xyz, const float* __restrict__ slab_t,
     const float* __restrict__ slab_dt, int64_t* __restrict__ rays_a, float* __restrict__ xyzs,
     float* __restrict__ dirs, float* __restrict__ deltas, float* __restrict__ ts, int32_t* __restrict__ counter) {
-    __shared__ int red[4], redl[4], redt[4];
+    __shared__ int red[4][3];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int b = blockIdx.x;
     // exclusive prefix over the workgroup sums [0, b) and the total of long rays: 16 loads per
@@ -127,40 +109,33 @@ __global__ __launch_bounds__(256) void march_train_place_kernel(
         pt[q] = q * 64 + lane < n ? st[q * 64 + lane] : 0.f;
         pd[q] = q * 64 + lane < n ? sd[q * 64 + lane] : 0.f;
     }
-    int acc = 0, lpre = 0, ltot = 0;  // samples before this workgroup, long rays before it, in all
+    int pre[3] = {0, 0, 0};  // samples before this workgroup, long rays before it, in all
 #pragma unroll
     for (int u = 0; u < PLACE_MAX_WG / 256; u++) {
         const int i = u * 256 + threadIdx.x;
         const int nl = (int)((unsigned)v[u] >> 26);
         if (i < b) {
-            acc += v[u] & ((1 << 26) - 1);
-            lpre += nl;
+            pre[0] += v[u] & ((1 << 26) - 1);
+            pre[1] += nl;
         }
-        ltot += nl;
+        pre[2] += nl;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        acc += __shfl_xor(acc, off, 64);
-        lpre += __shfl_xor(lpre, off, 64);
-        ltot += __shfl_xor(ltot, off, 64);
-    }
-    if (lane == 0) { red[wv] = acc; redl[wv] = lpre; redt[wv] = ltot; }
+    block_sum<3, 256>(pre, red);
+    int start = pre[0];
+    const int long_before = pre[1], long_total = pre[2];
     __syncthreads();
-    int start = red[0] + red[1] + red[2] + red[3];
-    const int long_before = redl[0] + redl[1] + redl[2] + redl[3];
-    const int long_total = redt[0] + redt[1] + redt[2] + redt[3];
-    __syncthreads();
-    if (lane == 0) red[wv] = n;
+    int* const len = &red[0][0];  // (red again, behind the barrier: the four waves' ray lengths)
+    if (lane == 0) len[wv] = n;
     __syncthreads();
     int lw = 0;  // long rays among the earlier waves of this workgroup
     for (int w = 0; w < wv; w++) {
-        start += red[w];
-        lw += red[w] > PLACE_LONG;
+        start += len[w];
+        lw += len[w] > PLACE_LONG;
     }
     const int64_t row = n > PLACE_LONG ? (int64_t)(long_before + lw)
                                        : (int64_t)long_total + (4 * (int64_t)b - long_before) + (wv - lw);
     if (b == (int)gridDim.x - 1 && threadIdx.x == 0) {
-        counter[0] = start + red[0] + red[1] + red[2] + red[3];  // (thread 0: start = the workgroup's prefix)
+        counter[0] = start + len[0] + len[1] + len[2] + len[3];  // (thread 0: start = the workgroup's prefix)
         counter[1] = (int32_t)R;
     }
     if (!live) return;

@@ -1,7 +1,7 @@
 // Test rendering: the serial compositor of alive rays, the compaction of the test marcher's output
 // and the device-driven test loop.
 #pragma once
-#include "common.h"
+#include "workgroup.h"
 
 namespace ncn {
 
@@ -46,24 +46,6 @@ __global__ __launch_bounds__(256) void composite_test_kernel(const float* __rest
     }
 }
 
-// Exclusive scan of v over the 256 threads of a workgroup (wsum: 4 LDS words), total = the sum.
-__device__ __forceinline__ int tl_block_excl(int v, int& total, int* wsum) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    __syncthreads();  // (wsum reuse)
-    if (lane == 63) wsum[wid] = incl;
-    __syncthreads();
-    int pre = 0;
-    for (int w = 0; w < wid; w++) pre += wsum[w];
-    total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    return pre + incl - v;
-}
-
 // Compaction of the test marcher's output (the fused test-render iteration): the valid samples of
 // every alive ray (its first n_eff of NS slots) copied to consecutive rows of xyz_c / dir_c, ray n's
 // rows starting at offsets[n]; count[0] = the total.  A workgroup scans its 256 rays' n_eff and
@@ -77,25 +59,12 @@ __global__ __launch_bounds__(256) void test_compact_kernel(const float* __restri
     __shared__ int wsum[4];
     __shared__ int base;
     const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int c = n < A ? n_eff[n] : 0;
-    // (tl_block_excl's scan, kept in place: through the function the kernel's register line moves, 52 -> 47 VGPRs)
-    int incl = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) wsum[wid] = incl;
+    int tot;
+    const int excl = block_excl_scan<256>(c, tot, wsum);
+    if (threadIdx.x == 0) base = tot ? atomicAdd(count, tot) : 0;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const int tot = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        base = tot ? atomicAdd(count, tot) : 0;
-    }
-    __syncthreads();
-    int pre = base;
-    for (int w = 0; w < wid; w++) pre += wsum[w];
-    const int off = pre + incl - c;
+    const int off = base + excl;
     if (n >= A) return;
     offsets[n] = off;
     const float* X = xyzs + n * (int64_t)NS * 3;
@@ -133,19 +102,16 @@ __global__ __launch_bounds__(256) void test_index_kernel(const int32_t* __restri
     __shared__ int base;
     int cnt = 0;
     for (int64_t i = lo + threadIdx.x; i < hi; i += 256) cnt += n_eff[i];
-    int total;
-    (void)tl_block_excl(cnt, total, wsum);
+    const int total = block_sum<256>(cnt, wsum);
     if (threadIdx.x == 0) base = total ? atomicAdd(ctrl + 4, total) : 0;
     __syncthreads();
     int run = base;
     for (int64_t c0 = lo; c0 < hi; c0 += 256) {
         const int64_t n = c0 + threadIdx.x;
         const int c = n < hi ? n_eff[n] : 0;
-        int tot;
-        const int off = run + tl_block_excl(c, tot, wsum);
+        const int off = block_excl_sweep<256>(c, run, wsum);
         const int first = (int)(n * NS);
         for (int s = 0; s < c; s++) idx[off + s] = first + s;
-        run += tot;
     }
 }
 // After the compositor: the rays it kept (alive >= 0) compacted into alive_next (order irrelevant:
@@ -161,18 +127,15 @@ __global__ __launch_bounds__(256) void test_alive_compact_kernel(const int64_t* 
     __shared__ int base;
     int cnt = 0;
     for (int64_t i = lo + threadIdx.x; i < hi; i += 256) cnt += alive[i] >= 0;
-    int total;
-    (void)tl_block_excl(cnt, total, wsum);
+    const int total = block_sum<256>(cnt, wsum);
     if (threadIdx.x == 0) base = total ? atomicAdd(ctrl + 5, total) : 0;
     __syncthreads();
     int run = base;
     for (int64_t c0 = lo; c0 < hi; c0 += 256) {
         const int64_t n = c0 + threadIdx.x;
         const int64_t r = n < hi ? alive[n] : -1;
-        int tot;
-        const int off = run + tl_block_excl(r >= 0, tot, wsum);
+        const int off = block_excl_sweep<256>((int)(r >= 0), run, wsum);
         if (r >= 0) alive_next[off] = r;
-        run += tot;
     }
 }
 __global__ void test_loop_next_kernel(int32_t* __restrict__ ctrl, int64_t* __restrict__ total, int n_rays,

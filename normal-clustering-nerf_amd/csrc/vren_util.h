@@ -2,6 +2,7 @@
 // marcher backward's segment sums.
 #pragma once
 #include "vren_march.h"
+#include "workgroup.h"
 
 namespace ncn {
 
