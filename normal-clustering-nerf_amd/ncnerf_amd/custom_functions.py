@@ -6,6 +6,7 @@ import torch
 from torch.amp import custom_bwd, custom_fwd
 
 from . import vren
+from ._lib import call, check_input
 
 
 class RayAABBIntersector(torch.autograd.Function):
@@ -82,6 +83,46 @@ class VolumeRenderer(torch.autograd.Function):
                                                              sigmas, raws, ws, deltas, ts, rays_a, opacity, depth,
                                                              rend, ctx.T_threshold)
         return dL_dsigmas, dL_draws, None, None, None, None
+
+
+class ExtraChannels(torch.autograd.Function):
+    """Extra channels composited through the compositor's weights (ncn_composite_extra_fw / _bw; no
+    reference counterpart: the reference widens its one compositor): rend[r] = sum over ray r's
+    samples of ws[s] raws[s], ws the weights VolumeRenderer returns -> rend (R, C), 1 <= C <= 51.
+    The training render sends the pred_norm / pred_sem channels through this node, so rgb keeps the
+    3-channel compositor; dL/dws reaches that compositor's backward through autograd.  Rows of ws /
+    raws outside every ray's range are never read and get zero gradients."""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, ws, raws, rays_a):
+        ws, raws, rays_a = ws.contiguous(), raws.contiguous(), rays_a.contiguous()
+        for t, n in ((ws, "ws"), (raws, "raws"), (rays_a, "rays_a")):
+            check_input(t, n)
+        if raws.dim() != 2 or ws.dim() != 1 or raws.shape[0] != ws.shape[0] or not 1 <= raws.shape[1] <= 51:
+            raise ValueError(f"ExtraChannels: ws (S) and raws (S, 1..51) expected, got {tuple(ws.shape)} and "
+                             f"{tuple(raws.shape)}")
+        if rays_a.dtype != torch.int64 or rays_a.dim() != 2 or rays_a.shape[1] != 3:
+            raise ValueError("ExtraChannels: rays_a must be (R, 3) int64")
+        R, C = rays_a.shape[0], raws.shape[1]
+        # (zeros: a ray index that rays_a does not list keeps a zero row)
+        rend = torch.zeros(R, C, dtype=torch.float32, device=ws.device)
+        call("ncn_composite_extra_fw", ws, raws, rays_a, R, ws.shape[0], C, rend)
+        ctx.save_for_backward(ws, raws, rays_a)
+        ctx.set_materialize_grads(False)
+        return rend
+
+    @staticmethod
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, dL_drend):
+        ws, raws, rays_a = ctx.saved_tensors
+        if dL_drend is None:
+            return None, None, None
+        # (zeros: the kernel writes the rows of the rays' ranges only, e.g. not a static step's capacity tail)
+        dL_dws, dL_draws = torch.zeros_like(ws), torch.zeros_like(raws)
+        call("ncn_composite_extra_bw", dL_drend.contiguous().float(), ws, raws, rays_a, rays_a.shape[0], ws.shape[0],
+             raws.shape[1], dL_dws, dL_draws)
+        return dL_dws, dL_draws, None
 
 
 class CountJob:

@@ -28,8 +28,16 @@ Pose refinement (train_nerf.py --optimize_ext: the prediction's rays require gra
 back-propagates into rays_o / rays_d (`ncn_normals_bwd_rays`), NeRFMTLoss.forward then takes the
 unfused `_Normals` + `cluster_losses` branch, and the fused nodes, which stop at the depth, raise.
 
-Not provided (weight 0 in every reference config, hyperparameters.py:33-49): semantic,
-Manhattan-NeRF and the canonical-direction terms (raise if enabled).
+The semantic term (losses.py:568-573; `loss_sem_w > 0` with `pred_sem` and `load_sem_gt` in the
+hyper-parameters, as the reference asserts): loss_sem_w * CE(pred['sem'][:gt_l], target['semantics'] - 1,
+ignore_index=-1), label 0 = void.  It stays on the device (torch's cross_entropy, summed and divided
+by the clamped count of labelled rays, no host read: capturable); a batch whose labels are all void
+gives exactly 0 and exactly zero gradients, where the reference's mean over no element is the NaN
+its validity filter replaces by 0.
+
+Not provided (weight 0 in every reference config, hyperparameters.py:33-49): the Manhattan-NeRF and
+canonical-direction terms (raise if enabled; the reference's own asserts, losses.py:227-231, make its
+Manhattan-NeRF branch unreachable).
 """
 import einops
 import numpy as np
@@ -490,9 +498,17 @@ class NeRFMTLoss(nn.Module):
         self.random_tr_poses = h.get("random_tr_poses", False)
         self.pred_norm_depth = h.get("pred_norm_depth", False)
         self.kmeans_seed = h.get("kmeans_seed", 1234)
-        for name in ("sem_w", "manhattan_nerf_w", "norm_D_C_can_dot_w", "norm_D_C_can_L1_w"):
+        for name in ("manhattan_nerf_w", "norm_D_C_can_dot_w", "norm_D_C_can_L1_w"):
             if getattr(self, name) > 0:
                 raise NotImplementedError(f"loss term {name} is not part of the ported hot path (0 in all configs)")
+        if self.sem_w > 0:  # losses.py:233-239
+            if not h.get("pred_sem", False):
+                raise NotImplementedError("loss_sem_w > 0 needs the semantic head: pred_sem in the hyper-parameters "
+                                          "(the reference asserts it, losses.py:239) and NGPMT(pred_sem=True, "
+                                          "n_sem_cls=K)")
+            if not h.get("load_sem_gt", False) or h.get("load_sem_WF_gt", False):  # losses.py:235-236 (asserts there)
+                raise ValueError("loss_sem_w > 0 needs load_sem_gt and not load_sem_WF_gt in the hyper-parameters: "
+                                 "the term reads the batch's `semantics` labels")
         if self.norm_DEpth_L1_w > 0 or self.norm_DEpth_dot_w > 0:
             self.norm_GT = "normals_depth" if h.get("loss_norm_GT_depth", False) else "normals"
         start = h.get("loss_norm_can_start", 0)
@@ -525,7 +541,8 @@ class NeRFMTLoss(nn.Module):
         settings (rgb + opacity + clustering terms on patch-sampled depth normals, nothing else) plus
         the batch facts: n_rays supervised rays that are all the rendered ones (n_opacity), whole
         64-ray patches with the standard 8x8 offsets `off`, no ray gradients (pose refinement)."""
-        return (not rays_grad and self.clustering and self.pred_norm_depth and not self.random_tr_poses
+        return (not rays_grad and self.sem_w == 0 and self.clustering and self.pred_norm_depth
+                and not self.random_tr_poses
                 and self.opacity_w > 0 and self.distortion_w == 0
                 and self.ray_sampling_strategy in ("all_images_triang_patch", "same_image_triang_patch")
                 and self.depth_w == 0 and self.norm_DEpth_L1_w == 0 and self.norm_DEpth_dot_w == 0
@@ -708,5 +725,18 @@ class NeRFMTLoss(nn.Module):
                 loss_d["norm_D_C_centr_dot"] = terms[1]
                 loss_d["norm_D_C_centr_L1"] = terms[2]
                 self.last_cluster = (labels, cents, raw)
+        if self.sem_w > 0:  # losses.py:568-573
+            loss_d["sem"] = self._semantic(head(pred_raw["sem"]), target_raw["semantics"])
         loss_d["total"] = sum(lo for lo in loss_d.values())
         return loss_d
+
+    def _semantic(self, logits, labels):
+        """loss_sem_w * CrossEntropyLoss(ignore_index=-1)(logits, labels - 1) (losses.py:240-242: label 0
+        is void), then the validity filter; the mean as sum / max(count, 1), so an all-void batch gives
+        an exact 0 with exact zero gradients instead of the 0 / 0 the filter would have to replace."""
+        if not logits.is_cuda:
+            raise RuntimeError("sem must be a CUDA tensor")
+        t = labels.reshape(-1).long() - 1
+        ce = F.cross_entropy(logits.float(), t, ignore_index=-1, reduction="sum")
+        count = (t != -1).sum().clamp_min(1).to(ce.dtype)
+        return self._validity(self.sem_w * (ce / count), logits.device)

@@ -24,8 +24,16 @@ analytic normal.  dL/dd leaves the MLP backward, dL/dx is one more hash-grid gat
 internal fp16 GradScaler an overflowed backward leaves non-finite input gradients (the step the
 optimizer skips): the caller skips its pose update too.
 
-Not provided (off in every reference config, hyperparameters.py:26-30): pred_sem / pred_norm heads,
-rgb_act='None' exposure tonemappers.
+Heads (ngp_mt.py:116-140, 222-227): `NGPMT(..., pred_sem=True, n_sem_cls=K, pred_norm=True)` adds
+sem_net / norm_net, tcnn FullyFusedMLP(16 -> 64 -> 64 -> K / 3) on the 16 sigma_net features h
+(include/ncnerf_heads.h, csrc/heads.hip).  Their parameters `sem_net.params` / `norm_net.params` are
+appended to the flat buffers behind W5 (every existing offset stays), `forward` also returns 'sems'
+(N, K) / 'norms' (N, 3), and the backward runs the split MLP pass with each head's backward between
+its two parts: the head adds its dL/dh into the stash the sigma part consumes.  With both heads off
+every path is what it was.  Not with a head: sort_samples, input gradients (dL/dx, dL/dd).
+
+Not provided (off in every reference config, hyperparameters.py:26-30): rgb_act='None' exposure
+tonemappers.
 """
 import math
 
@@ -48,6 +56,20 @@ ENC_BYTES = 64  # NCN_ENC_BYTES_PER_SAMPLE
 SORT_MIN_SAMPLES = 8192  # training batches at least this large are evaluated in Morton-window order
 W_SIGMA = 64 * 32 + 16 * 64
 W_RGB = N_W - W_SIGMA
+HEAD_MAX_OUT = 48  # NCN_HEAD_MAX_OUT: three 16-row output tiles
+N_HEAD_PACKED_HALVES = 16384  # NCN_HEAD_PACKED_HALVES
+
+
+def head_shapes(n_out):
+    """tcnn's padded shapes of a head FullyFusedMLP(16 -> 64 -> 64 -> n_out): the output rows padded
+    to a multiple of 16 (NCN_HEAD_NW(n_out) = 1024 + 4096 + 64 * 16 * ceil(n_out / 16) weights)."""
+    if not isinstance(n_out, int) or isinstance(n_out, bool) or not 1 <= n_out <= HEAD_MAX_OUT:
+        raise ValueError(f"a head has 1..{HEAD_MAX_OUT} outputs (got {n_out!r})")
+    return ((64, 16), (64, 64), (16 * ((n_out + 15) // 16), 64))
+
+
+def head_nw(n_out):
+    return sum(o * i for o, i in head_shapes(n_out))
 
 
 def grid_levels(scale, n_levels=L_LEVELS, log2_T=LOG2_T, n_min=N_MIN):
@@ -160,6 +182,65 @@ class _FieldFunction(torch.autograd.Function):
         return dL_dx, dL_dd, None, None, None, None, None, None
 
 
+class _FieldHeadsFunction(torch.autograd.Function):
+    """_FieldFunction of a model with heads: ncn_field_fwd, then ncn_head_fwd per head on the encoding
+    cache -> (sigmas, rgbs, one (N, n_out) output per head in the model's head order).  Backward:
+    ncn_field_bwd_mlp_part part 1 (rgb_net, its dL/dh into the stash), ncn_head_bwd per head (weight
+    gradients; its dL/dh added into the stash), part 2 (TruncExp, sigma_net, the encoding gradient),
+    the table scatter and the weight-gradient reductions.  No input gradients."""
+
+    @staticmethod
+    def forward(ctx, x, d, n_dev, model, *params):
+        need_grad = any(ctx.needs_input_grad[4:])
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            raise NotImplementedError("input gradients (dL/dx, dL/dd) are not available with a pred_sem / pred_norm head")
+        # (the encoding cache is the heads' input: needed as scratch at inference too)
+        sigmas, rgbs, enc, packed, _ = model._field_fwd(x, d, n_dev, 0, True)
+        n = x.shape[0]
+        outs = []
+        for name, n_out, _, _ in model._heads:
+            o = torch.empty(n, n_out, dtype=torch.float32, device=x.device)
+            if n > 0:
+                call("ncn_head_fwd", enc, n, n_dev, packed, model._head_packed[name], n_out, model._prec, o)
+            outs.append(o)
+        if need_grad:
+            ctx.save_for_backward(x, d, enc, packed, n_dev, *[model._head_packed[h[0]] for h in model._heads])
+            ctx.model = model
+        ctx.set_materialize_grads(False)
+        return (sigmas, rgbs) + tuple(outs)
+
+    @staticmethod
+    def backward(ctx, dL_dsigmas, dL_drgbs, *dL_dheads):
+        x, d, enc, packed, n_dev, *head_packed = ctx.saved_tensors
+        model = ctx.model
+        n, dev = x.shape[0], x.device
+        none = (None,) * (4 + 3 + len(model._heads))
+        if n == 0:
+            return none
+        L = _lib.lib()
+        c = lambda t: None if t is None else t.contiguous().float()
+        scale = model._bwd_loss_scale()
+        g_table, g_w = model._grad_views()
+        nb = (int(L.ncn_field_bwd_part_blocks(n, 1)), int(L.ncn_field_bwd_part_blocks(n, 2)))
+        slab = torch.empty(max(nb) * N_W, dtype=torch.float32, device=dev)
+        dE_ws = torch.empty(int(L.ncn_field_bwd_dE_floats(n)), dtype=torch.float32, device=dev)
+        stash = torch.empty(int(L.ncn_field_bwd_stash_floats(n)), dtype=torch.float32, device=dev)
+        lmax = model._level_max()
+        call("ncn_field_bwd_mlp_part", x, d, n, n_dev, None, packed, model._prec, enc, None, None, c(dL_drgbs), scale,
+             1, nb[0], slab, dE_ws, lmax, stash)
+        nbh = int(L.ncn_head_bwd_blocks(n))
+        for (name, n_out, off, n_w), hp, g in zip(model._heads, head_packed, dL_dheads):
+            if g is None:
+                continue
+            hslab = torch.empty(nbh * n_w, dtype=torch.float32, device=dev)
+            call("ncn_head_bwd", enc, n, n_dev, packed, hp, n_out, model._prec, c(g), scale, hslab, stash)
+            call("ncn_head_reduce_wgrad", hslab, nbh, n_w, model._flat_grad[off:off + n_w])
+        call("ncn_field_bwd_mlp_part", x, d, n, n_dev, None, packed, model._prec, enc, c(dL_dsigmas), None, None, scale,
+             2, nb[1], slab, dE_ws, lmax, stash)
+        model._scatter(x, n, n_dev, None, dE_ws, lmax, g_table, wgrad=(slab, nb[1], nb[0], g_w))
+        return none
+
+
 class NGPMT(nn.Module):
     def _bwd_loss_scale(self):
         """The field backward's loss_scale operand (ncn_field_bwd): the internal GradScaler's scale,
@@ -200,8 +281,17 @@ class NGPMT(nn.Module):
         self._prec = PRECISIONS[precision]
         if rgb_act != "Sigmoid":
             raise NotImplementedError("rgb_act='None' (exposure tonemappers) is off in every reference config")
-        if pred_sem or pred_norm:
-            raise NotImplementedError("pred_sem / pred_norm heads are off in every reference config")
+        pred_sem, pred_norm = bool(pred_sem), bool(pred_norm)
+        heads = []  # (module name, outputs) in the reference's module order (ngp_mt.py:116-140)
+        if pred_sem:
+            if kwargs.get("n_sem_cls") is None:
+                raise NotImplementedError("pred_sem=True needs the class count: pass n_sem_cls (the reference reads "
+                                          "kwargs['n_sem_cls'], ngp_mt.py:119)")
+            head_shapes(kwargs["n_sem_cls"])  # (ValueError outside 1..48)
+            heads.append(("sem_net", kwargs["n_sem_cls"]))
+            self.n_sem_cls = kwargs["n_sem_cls"]
+        if pred_norm:
+            heads.append(("norm_net", 3))
         self.pred_sem, self.pred_norm, self.rgb_act = pred_sem, pred_norm, rgb_act
         self.scale = scale
         self.register_buffer("center", torch.zeros(1, 3))
@@ -220,7 +310,12 @@ class NGPMT(nn.Module):
         self._xyz_extent = float(np.float32(scale) - np.float32(-scale))
         n_table = self.n_entries * F_PER_LEVEL
         self._n_table = n_table
-        flat = torch.zeros(n_table + N_W)
+        # heads behind W5: (module name, outputs, offset in the flat buffer, weights)
+        self._heads, off = [], n_table + N_W
+        for name, n_out in heads:
+            self._heads.append((name, n_out, off, head_nw(n_out)))
+            off += head_nw(n_out)
+        flat = torch.zeros(off)
         g = torch.Generator().manual_seed(seed)
         flat[:n_table] = (torch.rand(n_table, generator=g) * 2 - 1) * 1e-4  # tcnn grid init U(-1e-4, 1e-4)
         off = n_table
@@ -228,12 +323,20 @@ class NGPMT(nn.Module):
             a = math.sqrt(6.0 / (o + i))
             flat[off:off + o * i] = (torch.rand(o * i, generator=g) * 2 - 1) * a
             off += o * i
+        for _, n_out, _, _ in self._heads:  # (drawn after W1..W5: the field's initialisation is the heads-off one)
+            for o, i in head_shapes(n_out):
+                a = math.sqrt(6.0 / (o + i))
+                flat[off:off + o * i] = (torch.rand(o * i, generator=g) * 2 - 1) * a
+                off += o * i
         self._flat = flat
         self.xyz_encoder = _ParamHolder(flat[:n_table])
         self.sigma_net = _ParamHolder(flat[n_table:n_table + W_SIGMA])
-        self.rgb_net = _ParamHolder(flat[n_table + W_SIGMA:])
+        self.rgb_net = _ParamHolder(flat[n_table + W_SIGMA:n_table + N_W])
+        for name, _, off, n_w in self._heads:
+            setattr(self, name, _ParamHolder(flat[off:off + n_w]))
         self._flat_grad = None
         self._packed = None
+        self._head_packed = {}
         # AMP GradScaler state {scale, growth tracker} of the fp16 MLP (the reference trains with
         # precision=16, train_nerf.py:954: the scaled loss keeps tcnn's fp16 backward from
         # underflowing): the field backward multiplies its upstream gradients by the scale and
@@ -253,20 +356,25 @@ class NGPMT(nn.Module):
         self._deferred_graph = []  # the captured step's coarse-level scatters (Trainer._capture), every replay
 
     # -- flat buffers --------------------------------------------------------------------------
+    def _param_slices(self):
+        """(parameter, start, end) of every parameter in the flat buffers, in their order."""
+        n_table = self._n_table
+        return ([(self.xyz_encoder.params, 0, n_table), (self.sigma_net.params, n_table, n_table + W_SIGMA),
+                 (self.rgb_net.params, n_table + W_SIGMA, n_table + N_W)]
+                + [(getattr(self, name).params, off, off + n_w) for name, _, off, n_w in self._heads])
+
     def _apply(self, fn, recurse=True):
-        # keep the three parameters as views of one flat buffer across .to()/.cuda()
+        # keep the parameters as views of one flat buffer across .to()/.cuda()
         super()._apply(fn, recurse)
         flat = fn(self._flat)
-        n_table = self._n_table
-        flat[:n_table].copy_(self.xyz_encoder.params.data)
-        flat[n_table:n_table + W_SIGMA].copy_(self.sigma_net.params.data)
-        flat[n_table + W_SIGMA:].copy_(self.rgb_net.params.data)
+        for p, a, b in self._param_slices():
+            flat[a:b].copy_(p.data)
         self._flat = flat
-        self.xyz_encoder.params.data = flat[:n_table]
-        self.sigma_net.params.data = flat[n_table:n_table + W_SIGMA]
-        self.rgb_net.params.data = flat[n_table + W_SIGMA:]
+        for p, a, b in self._param_slices():
+            p.data = flat[a:b]
         self._flat_grad = None
         self._packed = None
+        self._head_packed = {}
         return self
 
     def flat_params(self):
@@ -278,19 +386,18 @@ class NGPMT(nn.Module):
         return self._flat_grad
 
     def _grad_views(self):
-        ps = (self.xyz_encoder.params, self.sigma_net.params, self.rgb_net.params)
         if self._flat_grad is None or self._flat_grad.device != self._flat.device:
             self._flat_grad = torch.zeros_like(self._flat)
         fg, n_table = self._flat_grad, self._n_table
-        views = (fg[:n_table], fg[n_table:n_table + W_SIGMA], fg[n_table + W_SIGMA:])
-        for p, v in zip(ps, views):
+        for p, a, b in self._param_slices():
+            v = fg[a:b]
             if p.grad is None or p.grad.data_ptr() != v.data_ptr():
                 if p.grad is not None:
                     v.copy_(p.grad)
                 else:
                     v.zero_()
                 p.grad = v
-        return fg[:n_table], fg[n_table:]
+        return fg[:n_table], fg[n_table:n_table + N_W]
 
     def grad_buckets(self, split):
         """The flat gradient as (levels [split, 16) of the table + the MLP weights, levels [0, split)):
@@ -337,6 +444,9 @@ class NGPMT(nn.Module):
         the packed MLP fragments itself (no pack launch between it and the next forward).  pack_inv
         (NCN_FIELD_NW x 2 int32, -1 = none) lists each master weight's packed elements, from
         ncn_field_pack_map; built once.  The packed buffer is allocated (and packed) if needed."""
+        if self._heads:
+            raise RuntimeError("pack_target: ncn_adam_step_packed refreshes the field's fragments only; a model with "
+                               "heads takes ncn_adam_step and packs explicitly (FlatAdam does)")
         if self._packed is None or self._packed.device != self._flat.device:
             self._pack_weights()
         inv = getattr(self, "_pack_inv", None)
@@ -357,6 +467,12 @@ class NGPMT(nn.Module):
         if self._packed is None or self._packed.device != self._flat.device:
             self._packed = torch.empty(N_PACKED_HALVES, dtype=torch.float16, device=self._flat.device)
         call("ncn_field_pack_weights", self._flat[self._n_table:], self._packed, self._prec)
+        for name, n_out, off, n_w in self._heads:
+            hp = self._head_packed.get(name)
+            if hp is None or hp.device != self._flat.device:
+                hp = self._head_packed[name] = torch.empty(N_HEAD_PACKED_HALVES, dtype=torch.float16,
+                                                           device=self._flat.device)
+            call("ncn_head_pack_weights", self._flat[off:off + n_w], n_out, hp, self._prec)
         return self._packed
 
     # -- field -----------------------------------------------------------------------------------
@@ -373,6 +489,9 @@ class NGPMT(nn.Module):
             enc = torch.empty(((n + 15) // 16) * 16 * ENC_BYTES // 2, dtype=torch.float16, device=dev)
         packed = self._take_packed()
         order = None
+        if self._heads and self.sort_samples:
+            raise NotImplementedError("sort_samples (the Morton-window processing order) is not supported with a "
+                                      "pred_sem / pred_norm head")
         if need_grad and self.sort_samples and n >= SORT_MIN_SAMPLES:
             # processing order: Morton-sorted windows of 4096 samples (ncn_field_sort_windows); the
             # encoding cache and the backward's dE are kept in it, the outputs stay in sample order
@@ -401,13 +520,24 @@ class NGPMT(nn.Module):
     def density(self, x, return_feat=False):
         """ngp_mt.py:157-171 (density-only kernel mode).  Differentiable w.r.t. the parameters and
         w.r.t. x (-d sigma / d x is the analytic normal): the sigma part of the MLP backward alone."""
-        if return_feat:
-            raise NotImplementedError("return_feat (the 16-d sigma_net feature) is only needed by the "
-                                      "pred_sem/pred_norm heads, which are not provided")
         _lib.check_input(x, "x")
+        if return_feat:
+            return self._density_feat(x.float().contiguous())
         sigmas, _ = _FieldFunction.apply(x.float().contiguous(), None, self.xyz_encoder.params,
                                          self.sigma_net.params, self.rgb_net.params, self, 1)
         return sigmas
+
+    @torch.no_grad()
+    def _density_feat(self, x):
+        """density(x, return_feat=True) -> (sigmas (N), h (N, 16) fp32), for inference and inspection
+        (no gradient): h, sigma_net's fp32 accumulators, is recomputed from the forward's encoding cache
+        with the field's own sigma_net code (ncn_head_feat): the h whose row 0 the kernel exponentiates."""
+        n = x.shape[0]
+        sigmas, _, enc, packed, _ = self._field_fwd(x, None, None, 1, True)
+        h = torch.empty(n, 16, dtype=torch.float32, device=x.device)
+        if n > 0:
+            call("ncn_head_feat", enc, n, None, packed, self._prec, h)
+        return sigmas, h
 
     def forward(self, x, d, **kwargs):
         """ngp_mt.py:196-229 -> {'sigmas': (N,), 'rgbs': (N,3)} (fp32).
@@ -419,6 +549,12 @@ class NGPMT(nn.Module):
         _lib.check_input(x, "x")
         _lib.check_input(d, "d")
         n_dev = kwargs.get("n_samples_dev")
+        if self._heads:
+            sigmas, rgbs, *outs = _FieldHeadsFunction.apply(x, d, n_dev, self, *[p for p, _, _ in self._param_slices()])
+            output = {"sigmas": sigmas, "rgbs": rgbs}
+            for (name, _, _, _), o in zip(self._heads, outs):
+                output["sems" if name == "sem_net" else "norms"] = o
+            return output
         sigmas, rgbs = _FieldFunction.apply(x, d, self.xyz_encoder.params, self.sigma_net.params,
                                             self.rgb_net.params, self, 0, n_dev)
         return {"sigmas": sigmas, "rgbs": rgbs}

@@ -39,8 +39,10 @@ class FlatAdam:
         # gate of a deferred step inside a captured graph (Trainer(defer_optimizer=True)): 0 = no
         # gradient pending, the step is skipped
         self.gate = torch.ones((), dtype=torch.int32, device=flat.device)
-        # refresh the model's packed MLP fragments inside the Adam pass (models with pack_target)
-        self.pack_fused = hasattr(model, "pack_target")
+        # refresh the model's packed MLP fragments inside the Adam pass (models with pack_target).  A model
+        # with heads has more weights behind the field's than ncn_adam_step_packed maps (it requires
+        # n - pack_off == NCN_FIELD_NW): it takes the plain step and packs explicitly.
+        self.pack_fused = hasattr(model, "pack_target") and not getattr(model, "_heads", None)
         if self.pack_fused:
             model.pack_target()  # (the map is built here, eagerly: a later first call may be inside a capture)
 
@@ -74,6 +76,8 @@ class FlatAdam:
             self.model._packed_fresh = True
         else:
             call("ncn_adam_step", *args)
+            if getattr(self.model, "_heads", None):
+                self.model.prepare_weights()  # (the field's and the heads' fragments of the updated weights)
 
     def state_tensors(self):
         """Every tensor the step mutates (parameters, moments, device counters)."""

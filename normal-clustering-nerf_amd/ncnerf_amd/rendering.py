@@ -21,7 +21,8 @@ import time
 import torch
 from einops import rearrange
 
-from .custom_functions import CountJob, RayAABBIntersector, RayMarcher, VolumeRenderer, VolumeRendererBg
+from .custom_functions import (CountJob, ExtraChannels, RayAABBIntersector, RayMarcher, VolumeRenderer,
+                               VolumeRendererBg)
 from . import _lib, vren
 
 
@@ -275,10 +276,10 @@ def render_rays_train(model, rays_o, rays_d, hits_t, **kwargs):
     output = model(xyzs, dirs, **kwargs)
     sigmas = output["sigmas"]
     raws = output["rgbs"]
-    if model.pred_norm:
-        raws = torch.cat((raws, output["norms"]), dim=-1)
-    if model.pred_sem:
-        raws = torch.cat((raws, output["sems"]), dim=-1)
+    # rgb alone goes through the compositor (it dispatches 1, 3, 4 or 6 channels, and fuses the
+    # background for 3); the heads' channels, norms then sems as in the reference's rend, are
+    # composited through its weights ws by a node of their own (ExtraChannels)
+    extras = ([output["norms"]] if model.pred_norm else []) + ([output["sems"]] if model.pred_sem else [])
     fuse_bg = exp_step_factor == 0 and raws.shape[1] == 3  # white background, rgb only
     renderer = VolumeRendererBg if fuse_bg else VolumeRenderer
     extra = (1.0,) if fuse_bg else ()
@@ -294,15 +295,17 @@ def render_rays_train(model, rays_o, rays_d, hits_t, **kwargs):
         sigmas, raws.contiguous(), results["deltas"], results["ts"], rays_a, kwargs.get("T_threshold", 1e-4), *extra)
     if job is not None and job.out is not None:
         results["_count_job"] = job
-    i = 3
-    results["rgb"] = rend if rend.shape[-1] == i else rend[..., :i]  # no slice node for rgb-only
-    if model.pred_norm:
-        results["norm_nn"] = rend[..., i:i + 3]
-        if kwargs.get("pred_norm_nn_norm", False):
-            results["norm_nn"] = torch.nn.functional.normalize(results["norm_nn"], p=2.0, dim=-1)
-        i += 3
-    if model.pred_sem:
-        results["sem"] = rend[..., i:i + kwargs["n_sem_cls"]]
+    results["rgb"] = rend if rend.shape[-1] == 3 else rend[..., :3]  # no slice node for rgb-only
+    if extras:
+        rend_x = ExtraChannels.apply(results["ws"], extras[0] if len(extras) == 1 else torch.cat(extras, dim=-1), rays_a)
+        i = 0
+        if model.pred_norm:
+            results["norm_nn"] = rend_x[..., :3]
+            if kwargs.get("pred_norm_nn_norm", False):
+                results["norm_nn"] = torch.nn.functional.normalize(results["norm_nn"], p=2.0, dim=-1)
+            i = 3
+        if model.pred_sem:
+            results["sem"] = rend_x[..., i:i + kwargs["n_sem_cls"]]
     results["rays_d"] = rays_d
     results["rays_o"] = rays_d  # rendering.py:227 (quirk q1)
     results["rays_a"] = rays_a

@@ -71,6 +71,11 @@ class Trainer:
         self.update_grid = update_grid
         self.render_kwargs = dict(near_distance=self.h["rend_near_dist"], max_samples=self.h["rend_max_samples"],
                                   test_time=False, random_bg=False, anneal_strategy="none", anneal_steps=0)
+        # a model with heads: the render slices its channels by these (rendering.py:120-148, 203-224)
+        if getattr(model, "pred_sem", False):
+            self.render_kwargs["n_sem_cls"] = model.n_sem_cls
+        if getattr(model, "pred_norm", False):
+            self.render_kwargs["pred_norm_nn_norm"] = bool(self.h.get("pred_norm_nn_norm", False))
         self.use_graph = use_graph
         self.split_backward = bool(split_backward) and use_graph
         self.split_fused = split_backward != "forked"
