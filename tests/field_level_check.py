@@ -69,8 +69,9 @@ def weight_tile_errors(got, ref):
 
 
 # ---- the edge set E: positions at, just inside, just outside and well outside the faces of the
-# world box [-0.5, 0.5]^3 (scale 0.5: x01 = x + 0.5), on cell boundaries of three levels, and
-# maximal runs (one position repeated) ----
+# world box [-scale, scale]^3 (scale 0.5: x01 = x + 0.5), on cell boundaries of three levels, and
+# maximal runs (one position repeated).  The in-box constants below are those of the unit box,
+# multiplied by the box's width 2 * scale (1.0, exactly, at the default) ----
 REPEAT = 600
 
 
@@ -78,16 +79,17 @@ def _f32(v):
     return np.float32(v)
 
 
-def edge_points(levels):
+def edge_points(levels, scale=0.5):
     """(special points (k, 3) f32, the repeated interior point (3,), the repeated face point (3,)),
-    world coordinates."""
-    lo, hi = _f32(-0.5), _f32(0.5)
+    world coordinates of the box [-scale, scale]^3 (`levels`: that scale's level table)."""
+    w = 2.0 * scale  # the box's width: 1.0 at scale 0.5, so every product below is the constant itself
+    lo, hi = _f32(-scale), _f32(scale)
     pts = []
     for cx in (lo, hi):  # the 8 corners, exactly
         for cy in (lo, hi):
             for cz in (lo, hi):
                 pts.append((cx, cy, cz))
-    inner = (_f32(0.13), _f32(-0.21))  # the in-face coordinates of the off-centre face points
+    inner = (_f32(0.13 * w), _f32(-0.21 * w))  # the in-face coordinates of the off-centre face points
     for axis in range(3):
         for side, face in ((-1.0, lo), (1.0, hi)):
             def put(v, others=(_f32(0.0), _f32(0.0))):
@@ -97,37 +99,38 @@ def edge_points(levels):
                 pts.append(tuple(p))
             put(face)  # the face centre, exactly
             put(np.nextafter(face, _f32(0.0)), inner)  # one ulp inside
-            put(np.nextafter(face, _f32(2.0 * side)), inner)  # one ulp outside
-            put(_f32(side * 0.7), inner)  # 0.1 outside: x01 = -0.2 / 1.2
-            put(_f32(side * 0.7), (_f32(side * 0.62), _f32(side * 0.58)))  # all three outside (low side: every floor < 0)
-            put(_f32(side * 0.7), (_f32(-side * 0.62), _f32(side * 0.58)))  # outside on both sides at once
+            put(np.nextafter(face, _f32(2.0 * side * w)), inner)  # one ulp outside
+            put(_f32(side * 0.7 * w), inner)  # 0.1 outside: x01 = -0.2 / 1.2
+            put(_f32(side * 0.7 * w), (_f32(side * 0.62 * w), _f32(side * 0.58 * w)))  # all three outside (low side: every floor < 0)
+            put(_f32(side * 0.7 * w), (_f32(-side * 0.62 * w), _f32(side * 0.58 * w)))  # outside on both sides at once
     # cell boundaries of levels 0, 5 and 10 (pos = scale x01 + 0.5 crosses an integer at
     # x01 = (k - 0.5) / scale): the floats just below and just above, on one axis and on all three
     for l in (0, 5, 10):
         s = float(np.float32(levels[l]["scale"]))
         res = levels[l]["res"]
         for k in (1, res // 2, res - 1):
-            exact = (k - 0.5) / s - 0.5  # world
+            exact = ((k - 0.5) / s - 0.5) * w  # world
             w0 = _f32(exact)
-            below = w0 if float(w0) <= exact else np.nextafter(w0, _f32(-1.0))
-            above = np.nextafter(below, _f32(1.0))
-            for w in (below, above):
-                pts.append((w, _f32(0.05), _f32(-0.3)))
+            below = w0 if float(w0) <= exact else np.nextafter(w0, _f32(-w))
+            above = np.nextafter(below, _f32(w))
+            for v in (below, above):
+                pts.append((v, _f32(0.05 * w), _f32(-0.3 * w)))
             pts.append((below, above, below))
     spec = np.array(pts, dtype=np.float32)
-    rep_in = np.array([0.2113, -0.0371, 0.3307], dtype=np.float32)
-    rep_face = np.array([-0.5, 0.17, -0.08], dtype=np.float32)  # x01 == 0 on x
+    rep_in = np.array([0.2113 * w, -0.0371 * w, 0.3307 * w], dtype=np.float32)
+    rep_face = np.array([-0.5 * w, 0.17 * w, -0.08 * w], dtype=np.float32)  # x01 == 0 on x
     return spec, rep_in, rep_face
 
 
-def place_edges(fill, levels):
-    """fill (n, 3) f32 world positions -> a copy with the edge set at the start of the array
+def place_edges(fill, levels, scale=0.5):
+    """fill (n, 3) f32 world positions -> a copy with the edge set (edge_points(levels, scale): the
+    box [-scale, scale]^3 and its level table) at the start of the array
     ([special, interior x 600, face x 600]), across index 4096 ([interior x 600, special, face x 600],
     the special points straddling 4096) and at the tail ([face x 600, special], as far as it does
     not overlap the block before), and the indices that hold an edge point."""
     x = np.array(fill, dtype=np.float32, copy=True)
     n = x.shape[0]
-    spec, rep_in, rep_face = edge_points(levels)
+    spec, rep_in, rep_face = edge_points(levels, scale)
     r_in, r_face = np.tile(rep_in, (REPEAT, 1)), np.tile(rep_face, (REPEAT, 1))
     mark = np.zeros(n, bool)
 

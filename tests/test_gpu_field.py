@@ -27,16 +27,18 @@ pytestmark = pytest.mark.gpu
 TOL = {"fp16": dict(rtol=2e-3, atol=1e-5, rgb=2e-3, bwd=2e-2), "bf16": dict(rtol=2e-2, atol=1e-4, rgb=1e-2, bwd=5e-2)}
 
 
-def _model_from_oracle(P, dev, precision="fp16", loss_scale=1.0):
+def _model_from_oracle(P, dev, precision="fp16", loss_scale=1.0, scale=0.5):
     """loss_scale: the AMP scale of the fp16 backward (NGPMT.amp_state; the training default is
     GradScaler's 2^16, sized for a real step's ~1e-5 upstream gradients).  These tests drive the
     backward with upstream gradients of order 1, which that scale would overflow (GradScaler then
-    skips the step and backs off), so they run it at 1 unless a test asks otherwise."""
-    m = NGPMT(scale=0.5, grid_size=128, precision=precision).to(dev)
+    skips the step and backs off), so they run it at 1 unless a test asks otherwise.
+    scale: the scene box's half width (P from field_ref.init_params at the same scale)."""
+    m = NGPMT(scale=scale, grid_size=128, precision=precision).to(dev)
     if loss_scale is not None and m.amp_state is not None:
         m.amp_state[0] = loss_scale
     flat = m.flat_params()
     n_table = m._n_table
+    assert n_table == P.table.numel()  # (the same level table)
     with torch.no_grad():
         flat[:n_table].copy_(P.table.reshape(-1))
         off = n_table
@@ -46,9 +48,11 @@ def _model_from_oracle(P, dev, precision="fp16", loss_scale=1.0):
     return m
 
 
-def _inputs(n, seed):
+def _inputs(n, seed, scale=0.5):
+    """Positions uniform in (0.999 of) the box [-scale, scale]^3 and unit directions (the box's
+    width 2 * scale is 1.0 at the default: the same floats as without it)."""
     g = torch.Generator().manual_seed(seed)
-    x = (torch.rand(n, 3, generator=g) - 0.5) * 0.999
+    x = (torch.rand(n, 3, generator=g) - 0.5) * 0.999 * (2.0 * scale)
     d = torch.randn(n, 3, generator=g)
     d = d / d.norm(dim=1, keepdim=True)
     return x, d

@@ -44,6 +44,35 @@ def test_static_shapes_render_matches_dynamic(dev):
     assert torch.equal(r0["ts"], r1["ts"][:S])
 
 
+def test_static_shapes_render_matches_dynamic_two_cascades(dev):
+    """The same at scale 1.0 (C = 2, a different bitfield per cascade), constant dt: the static-shape
+    path takes the one-launch marcher (ncn_march_train_fused at C > 1), the dynamic one the eager
+    marcher; 256 rays."""
+    import scale_cases as sc
+    from ncnerf_amd.rendering import _fused_march_ok
+    scene = SyntheticScene()
+    torch.manual_seed(7)
+    m = register_grid_buffers(NGPMT(scale=1.0, grid_size=128).to(dev))
+    assert m.cascades == 2
+    with torch.no_grad():
+        m.flat_params()[: m._n_table].uniform_(-1e-2, 1e-2)
+        m.density_bitfield.copy_(torch.from_numpy(np.array(sc.cascade_bitfield(2))).to(dev))
+    n = 256
+    b = scene.torch_batch(n, seed=3, device=dev)
+    noise = torch.rand(n, device=dev)
+    kw = dict(near_distance=0.01, max_samples=1024, march_noise=noise)
+    assert _fused_march_ok(m, dict(static_shapes=True, **kw), n) and not _fused_march_ok(m, dict(kw), n)
+    with torch.no_grad():
+        r0 = render(m, b["rays_o"], b["rays_d"], **kw)
+        r1 = render(m, b["rays_o"], b["rays_d"], static_shapes=True, **kw)
+    S = int(r0["rm_samples"])
+    assert S == int(r1["rm_samples"]) > 20 * n
+    assert r1["ts"].shape[0] == n * 1024  # capacity
+    for k in ("rgb", "depth", "opacity"):
+        assert torch.equal(r0[k], r1[k]), k
+    assert torch.equal(r0["ts"], r1["ts"][:S])
+
+
 def test_graph_step_matches_eager(dev):
     """Two eager runs give the run-to-run floor (float atomics in the table-gradient flush and the
     dW reduction sum in arrival order; Adam's m/sqrt(v) turns a sign flip of a near-zero gradient

@@ -57,3 +57,38 @@ def test_fused_test_render_bit_identical(dev, opaque, esf):
         assert sa["iterations"] <= sb["iterations"] <= sa["iterations"] + 1, (sa, sb)
     if opaque:
         assert float(a["opacity"].mean()) > 0.9  # the fitted model's rays do stop
+
+
+def test_fused_test_render_two_cascades(dev):
+    """The same at scale 1.0 (C = 2: march_test_kernel<false> and the device-driven loop at C > 1, the
+    field at extent 2), exponential stepping, a different bitfield per cascade, 4096 rays spread over
+    one image (the oracle's test marcher puts 83 % / 17 % of their first 64 samples in cascade 0 / 1):
+    the three loop modes bit-identical, iteration counts related as above."""
+    import numpy as np
+    import scale_cases as sc
+    scene = SyntheticScene()
+    torch.manual_seed(0)
+    m = register_grid_buffers(NGPMT(scale=1.0, grid_size=128).to(dev))
+    assert m.cascades == 2
+    with torch.no_grad():
+        m.density_bitfield.copy_(torch.from_numpy(np.array(sc.cascade_bitfield(2))).to(dev))
+        m.flat_params()[: m._n_table].mul_(3e4)  # densities of order 1: some rays stop, some march the budget
+    ro, rd = scene.image_rays(1, device=dev)
+    step = ro.shape[0] // 4096
+    o, d = ro[::step][:4096].contiguous(), rd[::step][:4096].contiguous()
+    outs = []
+    for fused in (False, "host", True):
+        st = {}
+        with torch.no_grad():
+            r = render(m, o, d, near_distance=0.01, max_samples=1024, test_time=True, test_fused=fused,
+                       exp_step_factor=1.0 / 256, loop_stats=st)
+        torch.cuda.synchronize()
+        outs.append((r, st))
+    (a, sa) = outs[0]
+    assert int(a["total_samples"]) > 4096 and sa["iterations"] > 1
+    assert 0.0 < float(a["opacity"].mean()) and bool(torch.isfinite(a["rgb"]).all())
+    for b, sb in outs[1:]:
+        for k in ("opacity", "depth", "rgb"):
+            assert torch.equal(a[k], b[k]), k
+        assert int(a["total_samples"]) == int(b["total_samples"])
+        assert sa["iterations"] <= sb["iterations"] <= sa["iterations"] + 1, (sa, sb)

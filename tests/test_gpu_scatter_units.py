@@ -47,22 +47,26 @@ def test_scatter_matches_serial_oracle(dev, n, op, mode):
     scatter_case(dev, n, op, mode)
 
 
-def scatter_case(dev, n, op, mode, xw=None, with_order=False, inf_level=12):
+def scatter_case(dev, n, op, mode, xw=None, with_order=False, inf_level=12, scale=0.5):
     """The body of test_scatter_matches_serial_oracle.  xw: the (n, 3) f32 world positions (default:
     samples on rays inside the box); with_order: the stored gradient is in the processing order of
     ncn_field_sort_windows on those positions and the scatter gathers the positions through it;
-    inf_level: the level of mode "inf"'s overflowed pair."""
-    m = NGPMT(scale=0.5, grid_size=128).to(dev)
-    levels = field_ref.grid_levels(0.5)[0]
-    if xw is None:
-        xw = (_ray_samples(n, seed=n) - np.float32(0.5)).astype(np.float32)  # world positions
+    inf_level: the level of mode "inf"'s overflowed pair; scale: the scene box's half width (the
+    model, its level table and the box of the default positions)."""
+    m = NGPMT(scale=scale, grid_size=128).to(dev)
+    levels = field_ref.grid_levels(scale)[0]
+    xyz_min, extent = np.float32(m._xyz_min), np.float32(m._xyz_extent)
+    if xw is None:  # world positions (an extent of 1.0 leaves the product as it is)
+        xw = ((_ray_samples(n, seed=n) - np.float32(0.5)) * extent).astype(np.float32)
     assert xw.shape == (n, 3) and xw.dtype == np.float32
     xyzs = torch.from_numpy(xw).to(dev)
     order = None
     if with_order:
         order = torch.empty(n, dtype=torch.int32, device=dev)
         assert _lib.call("ncn_field_sort_windows", xyzs, n, None, m._xyz_min, m._xyz_extent, order) == 0
-    x01 = (xw + np.float32(0.5)).astype(np.float32)  # what the kernel forms: (x - xyz_min) * (1 / extent), extent 1
+    # what the kernel forms: (x - xyz_min) / extent in f32 (a power-of-two extent multiplies by its
+    # exact reciprocal: the same float; extent 1 at the default scale: x + 0.5)
+    x01 = ((xw - xyz_min) / extent).astype(np.float32)
     rng = np.random.default_rng(n + 1)
     tdt = torch.float16 if op == "fp16" else torch.bfloat16
     S = 2.0 ** 23 if mode == "scaled" else 1.0

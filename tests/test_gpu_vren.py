@@ -8,9 +8,11 @@ import numpy as np
 import pytest
 import torch
 
+import scale_cases as sc
 from oracle import vren_ref
 from ncnerf_amd import vren
 from ncnerf_amd.synthetic import SyntheticScene
+from scale_cases import edge_rays as _edge_rays  # (shared with the host checks of the C > 1 cases)
 
 pytestmark = pytest.mark.gpu
 
@@ -18,17 +20,6 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def scene():
     return SyntheticScene()
-
-
-def _edge_rays(rng, n):
-    """Random rays plus the reference edge cases: misses, starts inside, axis-parallel (1/d = inf)."""
-    o = rng.uniform(-0.9, 0.9, (n, 3)).astype(np.float32)
-    d = rng.normal(size=(n, 3)).astype(np.float32)
-    d[: n // 8, 1:] = 0.0  # parallel to x
-    d[n // 8: n // 4, 0] = 0.0  # in the yz plane
-    o[n // 4: n // 3] = rng.uniform(-0.2, 0.2, (n // 3 - n // 4, 3))  # inside the box
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    return o, d
 
 
 def test_ray_aabb_bitexact(dev):
@@ -108,9 +99,9 @@ def _march_uniform_np(seed, ctr, n):
 
 class _Box:
     """The attributes march_train_fused reads from the model."""
-    def __init__(self, bitfield):
-        self._aabb = ((0.0, 0.0, 0.0), (0.5, 0.5, 0.5))
-        self.density_bitfield, self.cascades, self.scale, self.grid_size = bitfield, 1, 0.5, 128
+    def __init__(self, bitfield, scale=0.5, cascades=1):
+        self._aabb = ((0.0, 0.0, 0.0), (scale, scale, scale))
+        self.density_bitfield, self.cascades, self.scale, self.grid_size = bitfield, cascades, scale, 128
 
 
 @pytest.mark.parametrize("n,edge,ms", [(8192, False, 1024), (2048, True, 1024), (777, False, 64), (1, False, 1024),
@@ -172,6 +163,88 @@ def test_raymarching_train_exp_step_and_cascades(dev, scene):
     ref = vren_ref.raymarching_train(o, d, ht, bf, 2, 1.0, 1 / 256, noise, 128, 1024)
     for a, r in zip(out, ref):
         assert np.array_equal(a.cpu().numpy(), r)
+
+
+def _dev_copy(dev):
+    return lambda a: torch.from_numpy(np.array(a)).to(dev)  # (the shared case arrays are read-only)
+
+
+@pytest.mark.parametrize("n", sc.TRAIN_N)
+@pytest.mark.parametrize("name", sorted(sc.TRAIN_CASES))
+def test_raymarching_train_cascades_bitexact(dev, name, n):
+    """raymarching_train at C > 1 (tests/scale_cases.py TRAIN_CASES; a different bitfield per cascade,
+    edge rays scaled to the box plus ordinary rays from outside): c2_const / c3_const — constant dt at
+    scale 1.0 / 1.5, march_train_wave_kernel<false, 2>; c3_exp — exp_step_factor 1/256 at scale 1.5,
+    the serial walk march_train_walk_kernel<false> with samples whose mip comes from dt.  The oracle's
+    outputs hold samples of every mip (asserted on the host, tests/test_scale_cases_host.py)."""
+    case = sc.train_case(name, n)
+    T = _dev_copy(dev)
+    out = vren.raymarching_train(T(case["o"]), T(case["d"]), T(case["ht"]), T(case["bf"]), case["C"], case["scale"],
+                                 case["esf"], T(case["noise"]), sc.G, sc.MAX_SAMPLES)
+    for a, r, nm in zip(out, case["ref"], sc.NAMES):
+        a = a.cpu().numpy()
+        assert a.shape == r.shape, nm
+        assert np.array_equal(a, r), f"{name} n {n} {nm}: {np.argwhere(a != r)[:5]}"
+
+
+@pytest.mark.parametrize("n", sc.TRAIN_N)
+@pytest.mark.parametrize("name", ["c2_const", "c3_const"])
+def test_fused_marcher_cascades_bitexact(dev, name, n):
+    """ncn_march_train_fused at C > 1 (march_train_walk2_kernel<false, 2>: its own intersection with the
+    box of half width `scale`, near clamp, jitter, walk) on the rays of
+    test_raymarching_train_cascades_bitexact, with explicit noise and with the device RNG, as
+    test_fused_marcher_bitexact."""
+    from ncnerf_amd.rendering import march_train_fused
+    case = sc.train_case(name, n)
+    T = _dev_copy(dev)
+    box = _Box(T(case["bf"]), case["scale"], case["C"])
+    ms = sc.MAX_SAMPLES
+
+    def check(out, ref, tag):
+        S = int(ref[5][0])
+        ra = out["rays_a"].cpu().numpy()
+        long_ = ra[:, 2] > 256  # rays with > 256 samples first, each class in ray order
+        nl = int(long_.sum())
+        assert long_[:nl].all() and not long_[nl:].any()
+        assert np.all(np.diff(ra[:nl, 0]) > 0) and np.all(np.diff(ra[nl:, 0]) > 0)
+        for nm, r in zip(sc.NAMES, ref):
+            a = out[nm].cpu().numpy()
+            if nm == "rays_a":
+                a = a[np.argsort(a[:, 0], kind="stable")]
+            if nm in ("xyzs", "dirs", "deltas", "ts"):
+                a = a[:S]
+            assert np.array_equal(a, r), f"{name} n {n} {tag} {nm}: {np.argwhere(a != r)[:5]}"
+
+    for rep in range(2):
+        out = march_train_fused(box, T(case["o"]), T(case["d"]), 0.01, ms, noise=T(case["noise"]))
+        torch.cuda.synchronize()
+        check(out, case["ref"], f"rep {rep}")
+    seed, step = 1234567891234, 42
+    out = march_train_fused(box, T(case["o"]), T(case["d"]), 0.01, ms, rng=(seed, torch.tensor(step, device=dev)))
+    ref = vren_ref.raymarching_train(case["o"], case["d"], case["ht"], case["bf"], case["C"], case["scale"], 0.0,
+                                     _march_uniform_np(seed, step, n), sc.G, ms)
+    check(out, ref, "rng")
+
+
+@pytest.mark.parametrize("esf", sc.TEST_ESF)
+@pytest.mark.parametrize("scale", sc.TEST_SCALES)
+def test_raymarching_test_cascades_bitexact(dev, scale, esf):
+    """raymarching_test at C = 2 / 3 (march_test_kernel<false>), N_samples 1, 4, 64 on the same hits_t
+    (mutated by each call).  The reference passes `cascades` as calc_dt's scale (raymarching.cu:370,
+    :399): at esf 1/64 the rays from far outside carry samples whose dt sits at that clamp,
+    sqrt(3) 2 C / G, above the training marcher's sqrt(3) 2 scale / G (asserted on the host).  Found: no
+    defect; with `scale` in place of `(float)cascades` in march_test_kernel (a scratch build) the esf
+    1/64 cases and (1.0, 1/256) fail at their first sample past the training clamp."""
+    case = sc.eval_march_case(scale, esf)
+    T = _dev_copy(dev)
+    ht_dev = T(case["ht0"])
+    o, d, alive, bf = T(case["o"]), T(case["d"]), T(case["alive"]), T(case["bf"])
+    for N, (ref, ht_after) in zip(sc.TEST_NS, case["refs"]):
+        out = vren.raymarching_test(o, d, ht_dev, alive, bf, case["C"], scale, esf, sc.G, sc.MAX_SAMPLES, N)
+        for a, r, nm in zip(out, ref, ("xyzs", "dirs", "deltas", "ts", "n_eff")):
+            a = a.cpu().numpy()
+            assert np.array_equal(a, r), f"scale {scale} esf {esf} N {N} {nm}: {np.argwhere(a != r)[:5]}"
+        assert np.array_equal(ht_dev.cpu().numpy(), ht_after)  # hits_t mutation (raymarching.cu:390)
 
 
 def test_raymarching_test_bitexact(dev, scene):
