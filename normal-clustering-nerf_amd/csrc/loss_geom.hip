@@ -9,7 +9,8 @@
 //                         term and, given the rays, the normal terms through loss_normals.h's
 //                         tri_depth_grads
 //  * ncn_batch_labels_fw  labels[r] = plane[img_idxs[r]][pix_idxs[r]] beside ncn_batch_rays_fw
-// Nothing here reads the host but its arguments, allocates or synchronises: all three can be nodes of
+//  * ncn_batch_semantics_fw  the same gather of an integer label plane (include/ncnerf_sem.h)
+// Nothing here reads the host but its arguments, allocates or synchronises: all of them can be nodes of
 // a captured step.  The per-element terms are f32, operation for operation as torch evaluates the
 // reference's expressions (no contraction into fma).
 #pragma clang fp contract(off)
@@ -19,6 +20,7 @@
 #include "loss_normals.h"
 #include "workgroup.h"
 #include "../../include/ncnerf_geom.h"
+#include "../../include/ncnerf_sem.h"
 
 namespace ncn {
 
@@ -267,6 +269,23 @@ __global__ __launch_bounds__(GM_THREADS) void batch_labels_fw_kernel(
     }
 }
 
+// the integer plane (uint8, int32 or int64 labels): 0, void, where an index is out of range
+__global__ __launch_bounds__(GM_THREADS) void batch_semantics_fw_kernel(
+    const int64_t* __restrict__ img_idxs, const int64_t* __restrict__ pix_idxs, int64_t R,
+    const void* __restrict__ plane, int plane_bytes, int n_images, int64_t HW, int64_t* __restrict__ out) {
+    const int64_t r = (int64_t)blockIdx.x * GM_THREADS + threadIdx.x;
+    if (r >= R) return;
+    const int64_t im = img_idxs[r], px = pix_idxs[r];
+    int64_t v = 0;
+    if (im >= 0 && im < n_images && px >= 0 && px < HW) {
+        const int64_t at = im * HW + px;
+        v = plane_bytes == 1   ? (int64_t) static_cast<const uint8_t*>(plane)[at]
+            : plane_bytes == 4 ? (int64_t) static_cast<const int32_t*>(plane)[at]
+                               : static_cast<const int64_t*>(plane)[at];
+    }
+    out[r] = v;
+}
+
 }  // namespace ncn
 
 using namespace ncn;
@@ -354,6 +373,21 @@ int ncn_batch_labels_fw(const int64_t* img_idxs, const int64_t* pix_idxs, int64_
                        (hipStream_t)stream, img_idxs, pix_idxs, n_rays, depth, normals, normals_depth, n_images,
                        n_pixels, out_depth, out_normals, out_normals_depth);
     NCN_LAUNCH_CHECK("ncn_batch_labels_fw");
+    return 0;
+}
+
+int ncn_batch_semantics_fw(const int64_t* img_idxs, const int64_t* pix_idxs, int64_t n_rays, const void* plane,
+                           int plane_bytes, int n_images, int64_t n_pixels, int64_t* out, void* stream) {
+    NCN_REQUIRE(n_rays >= 0 && n_images >= 1 && n_pixels >= 1, hipErrorInvalidValue, "ncn_batch_semantics_fw: bad sizes");
+    NCN_REQUIRE(plane_bytes == 1 || plane_bytes == 4 || plane_bytes == 8, hipErrorInvalidValue,
+                "ncn_batch_semantics_fw: plane_bytes = %d; 1 (uint8), 4 (int32) or 8 (int64)", plane_bytes);
+    if (n_rays == 0) return 0;
+    NCN_REQUIRE(img_idxs != nullptr && pix_idxs != nullptr && plane != nullptr && out != nullptr, hipErrorInvalidValue,
+                "ncn_batch_semantics_fw: null argument");
+    NCN_REQUIRE(cdiv(n_rays, GM_THREADS) <= 0x7FFFFFFF, hipErrorInvalidValue, "ncn_batch_semantics_fw: too many rays");
+    hipLaunchKernelGGL(batch_semantics_fw_kernel, dim3((unsigned)cdiv(n_rays, GM_THREADS)), dim3(GM_THREADS), 0,
+                       (hipStream_t)stream, img_idxs, pix_idxs, n_rays, plane, plane_bytes, n_images, n_pixels, out);
+    NCN_LAUNCH_CHECK("ncn_batch_semantics_fw");
     return 0;
 }
 

@@ -3,6 +3,8 @@
 // their exact medians — behind the C ABI of include/ncnerf_metrics.h.
 //  * metrics_ssim.h    the LDS-tiled SSIM pass (both Gaussian SSIMs and the 7x7 one in one launch)
 //  * metrics_select.h  exact k-th smallest by three histogram passes
+//  * metrics_sem.h     the semantic confusion matrix of a view in one launch, and its scores
+//                      (include/ncnerf_sem.h)
 // Every sum has a fixed order: per thread, xor-shuffles per wave, the waves' totals in wave order,
 // the workgroups' partial sums by ONE workgroup (thread t takes partials t, t + 256, ...).  Partial
 // sums are doubles, so the order is also irrelevant to well below an f32 ulp.  No float atomics.
@@ -13,7 +15,9 @@
 #include "workgroup.h"
 #include "metrics_ssim.h"
 #include "metrics_select.h"
+#include "metrics_sem.h"
 #include "../../include/ncnerf_metrics.h"
+#include "../../include/ncnerf_sem.h"
 
 namespace ncn {
 
@@ -287,6 +291,34 @@ int ncn_metrics_finalise(const double* pw_sums, const int64_t* depth_count, int6
     hipLaunchKernelGGL(finalise_kernel, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, pw_sums, depth_count, n_rgb, ssim,
                        ang_sums, ang_counts, medians, row);
     NCN_LAUNCH_CHECK("ncn_metrics_finalise");
+    return 0;
+}
+
+int ncn_sem_confusion(const float* logits, int64_t row_stride, const int64_t* labels, int label_shift,
+                      int ignore_label, int64_t n_pix, int n_cls, int64_t* conf, int64_t* counts,
+                      int32_t* pred_labels, void* stream) {
+    static_assert(SEM_MAX_CLS == NCN_SEM_MAX_CLASSES, "ncnerf_sem.h and metrics_sem.h disagree");
+    NCN_REQUIRE(n_cls >= 1 && n_cls <= SEM_MAX_CLS, hipErrorInvalidValue, "ncn_sem_confusion: n_cls = %d, 1..%d", n_cls,
+                SEM_MAX_CLS);
+    NCN_REQUIRE(n_pix >= 0 && n_pix <= ((int64_t)1 << 40) && row_stride >= n_cls, hipErrorInvalidValue,
+                "ncn_sem_confusion: bad sizes (n_pix = %lld, row_stride = %lld, n_cls = %d)", (long long)n_pix,
+                (long long)row_stride, n_cls);
+    NCN_REQUIRE(conf != nullptr && counts != nullptr, hipErrorInvalidValue, "ncn_sem_confusion: null output");
+    if (n_pix == 0) return 0;
+    NCN_REQUIRE(logits != nullptr && labels != nullptr, hipErrorInvalidValue, "ncn_sem_confusion: null input");
+    hipLaunchKernelGGL(sem_confusion_kernel, dim3(stream_blocks(n_pix)), dim3(SEM_THREADS),
+                       4 * (size_t)sem_lds_words(n_cls), (hipStream_t)stream, logits, row_stride, labels,
+                       (int64_t)label_shift, (int64_t)ignore_label, n_pix, n_cls, conf, counts, pred_labels);
+    NCN_LAUNCH_CHECK("ncn_sem_confusion");
+    return 0;
+}
+
+int ncn_sem_finalise(const int64_t* conf, int n_cls, float* out, void* stream) {
+    NCN_REQUIRE(n_cls >= 1 && n_cls <= SEM_MAX_CLS, hipErrorInvalidValue, "ncn_sem_finalise: n_cls = %d, 1..%d", n_cls,
+                SEM_MAX_CLS);
+    NCN_REQUIRE(conf != nullptr && out != nullptr, hipErrorInvalidValue, "ncn_sem_finalise: null argument");
+    hipLaunchKernelGGL(sem_finalise_kernel, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, conf, n_cls, out);
+    NCN_LAUNCH_CHECK("ncn_sem_finalise");
     return 0;
 }
 

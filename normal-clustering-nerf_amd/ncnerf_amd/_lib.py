@@ -1,17 +1,17 @@
 """ctypes binding of libncnerf.so, derived from the C ABI declared in include/ncnerf.h, for the
 validation metrics in include/ncnerf_metrics.h, for the geometry supervision (the depth, GT-normal
 and RegNeRF loss terms, the label gather) in include/ncnerf_geom.h, for the isosurface extraction
-in include/ncnerf_mesh.h, and for the semantic / normal heads and the compositing of their channels in
-include/ncnerf_heads.h.
+in include/ncnerf_mesh.h, for the semantic / normal heads and the compositing of their channels in
+include/ncnerf_heads.h, and for the semantic metrics and the integer label gather in include/ncnerf_sem.h.
 
 This is the only place Python talks to the HIP kernels.  There is NO CPU fallback: if the library
 is missing, or a kernel is called with a CPU tensor, the call raises.  Tensors are passed as raw
 device pointers and sizes, on torch's *current* HIP stream (never the legacy default stream).
 
 The headers are the single statement of the ABI: parsed at import (ncnerf.h and ncnerf_metrics.h
-into the table ABI, ncnerf_geom.h, ncnerf_mesh.h and ncnerf_heads.h into tables of their own, GEOM_ABI, MESH_ABI and HEADS_ABI), they
-give every argtypes /
-restype, and `call` marshals plain arguments against them (see `marshal`) before anything is launched.
+into the table ABI, ncnerf_geom.h, ncnerf_mesh.h, ncnerf_heads.h and ncnerf_sem.h into tables of their
+own, GEOM_ABI, MESH_ABI, HEADS_ABI and SEM_ABI), they give every argtypes / restype, and `call`
+marshals plain arguments against them (see `marshal`) before anything is launched.
 """
 import ctypes
 import operator
@@ -27,6 +27,7 @@ METRICS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ncnerf_metrics
 GEOM_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ncnerf_geom.h")  # same grammar, all `int`
 MESH_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ncnerf_mesh.h")  # same grammar, all `int`
 HEADS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ncnerf_heads.h")  # same grammar, all `int`
+SEM_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ncnerf_sem.h")  # same grammar, all `int`
 
 P = ctypes.c_void_p
 I64 = ctypes.c_int64
@@ -171,18 +172,37 @@ def _parse_heads_header(tables):
     return heads
 
 
+def _read_sem_header():
+    try:
+        return open(SEM_HEADER_PATH).read()
+    except OSError as e:
+        raise NcnError(f"include/ncnerf_sem.h not found at {SEM_HEADER_PATH}: the binding of the semantic metrics "
+                       f"is derived from it ({e})") from None
+
+
+def _parse_sem_header(tables):
+    """The sixth header's table; a name that one of `tables` (the other headers') declares too is an error."""
+    sem = parse_header(_read_sem_header())
+    for name in sem:
+        if any(name in t for t in tables):
+            raise NcnError(f"{name} is declared in include/ncnerf_sem.h and in another header of include/")
+    return sem
+
+
 ABI = _parse_headers()
 GEOM_ABI = _parse_geom_header(ABI)
 TABLES = (ABI, GEOM_ABI)
 MESH_ABI = _parse_mesh_header(TABLES)
 ALL_TABLES = TABLES + (MESH_ABI,)  # what is bound beside the heads; TABLES stays the training / validation surface
 HEADS_ABI = _parse_heads_header(ALL_TABLES)
-BOUND_TABLES = ALL_TABLES + (HEADS_ABI,)  # every table lib() binds
+BOUND_TABLES = ALL_TABLES + (HEADS_ABI,)  # the tables bound before the semantic metrics came
+SEM_ABI = _parse_sem_header(BOUND_TABLES)
+LOADED_TABLES = BOUND_TABLES + (SEM_ABI,)  # every table lib() binds
 
 
 def declaration(name):
     """(restype, parameters) of an entry point, whichever header declares it."""
-    for table in BOUND_TABLES:
+    for table in LOADED_TABLES:
         decl = table.get(name)
         if decl is not None:
             return decl
@@ -191,7 +211,7 @@ def declaration(name):
 
 # name -> argtypes (stream last), as ctypes sees them
 SIGNATURES = dict((name, [P if kind == "ptr" else _SCALARS[kind] for kind, _, _ in params])
-                  for table in BOUND_TABLES for name, (_, params) in table.items())
+                  for table in LOADED_TABLES for name, (_, params) in table.items())
 
 _lib = None
 
@@ -212,7 +232,7 @@ def lib():
             raise NcnError(f"libncnerf.so not found at {LIB_PATH}: run __graft_entry__.build() "
                            f"(make -C normal-clustering-nerf_amd)")
         L = ctypes.CDLL(LIB_PATH)
-        for table in BOUND_TABLES:
+        for table in LOADED_TABLES:
             for name, (ret, _) in table.items():
                 fn = getattr(L, name)
                 fn.argtypes = SIGNATURES[name]
@@ -228,6 +248,11 @@ def exported_symbols():
 def heads_symbols():
     """The entry points of include/ncnerf_heads.h (bound by lib() like every other)."""
     return list(HEADS_ABI)
+
+
+def sem_symbols():
+    """The entry points of include/ncnerf_sem.h (bound by lib() like every other)."""
+    return list(SEM_ABI)
 
 
 def mesh_symbols():
@@ -296,7 +321,7 @@ def _marshaller(name, params):
     return ns["marshal"], (n - 1, n) if _launches(params) else (n,)
 
 
-_PLANS = {name: _marshaller(name, params) for table in BOUND_TABLES for name, (_, params) in table.items()}
+_PLANS = {name: _marshaller(name, params) for table in LOADED_TABLES for name, (_, params) in table.items()}
 
 
 def marshal(name, args):

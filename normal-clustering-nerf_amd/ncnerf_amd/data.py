@@ -7,7 +7,9 @@ get_rays) by two launches — ncn_batch_draw and ncn_batch_rays_fw — that read
 but a step counter, which may itself live on the device: with preallocated outputs they can be
 captured in a HIP graph.  A dataset that was given label planes (depth, normals, normals_depth: the
 targets of NeRFMTLoss's depth and GT-normal terms) gathers them for the drawn rays in a third launch,
-ncn_batch_labels_fw, and its batches carry them under those keys.  The batch is the dict
+ncn_batch_labels_fw, and its batches carry them under those keys; a `semantics` plane of integer
+class labels (the target of NeRFMTLoss's semantic term and of the semantic metrics; 0 = void) is
+gathered behind it by ncn_batch_semantics_fw into int64 labels.  The batch is the dict
 Trainer.step(batch, ...) takes; the Trainer itself does not draw from a dataset yet.
 With optimize_ext the dataset holds the reference's per-image pose corrections dR (axis-angle) and dT
 (train_nerf.py:244-249) and the rays carry their gradient (ncn_batch_rays_bw, deterministic).
@@ -72,6 +74,18 @@ def batch_labels_fw(img_idxs, pix_idxs, planes, out):
          *(out[k] if planes.get(k) is not None else None for k in LABEL_PLANES))
 
 
+_SEMANTICS_DTYPES = (torch.uint8, torch.int32, torch.int64)  # the widths ncn_batch_semantics_fw takes: 1, 4, 8
+
+
+def batch_semantics_fw(img_idxs, pix_idxs, plane, out):
+    """ncn_batch_semantics_fw: out[r] = plane[img_idxs[r], pix_idxs[r]] as int64 for plane (V, H*W) uint8,
+    int32 or int64; an index out of range gives 0 (void)."""
+    if plane.dtype not in _SEMANTICS_DTYPES:
+        raise RuntimeError(f"semantics must be torch.uint8, torch.int32 or torch.int64 (got {plane.dtype})")
+    call("ncn_batch_semantics_fw", img_idxs, pix_idxs, img_idxs.numel(), plane, plane.element_size(), plane.shape[0],
+         plane.shape[1], out)
+
+
 class _PoseRays(torch.autograd.Function):
     """rays_o, rays_d, rgb of a drawn batch as a function of dR, dT (train_nerf.py:177-182)."""
 
@@ -102,11 +116,12 @@ class DeviceRayDataset:
     reference's datasets keep it.  corner_mode "reference" keeps base.py:164-166's pixel arithmetic
     (DESIGN.md §3), "grid" draws patches that lie inside the image.  depth (V, H*W) or (V, H, W),
     normals and normals_depth (V, H*W, 3) or (V, H, W, 3), float32: optional label planes, gathered
-    into every batch under their names."""
+    into every batch under their names.  semantics (V, H*W) or (V, H, W), uint8, int32 or int64 (kept
+    in its dtype): optional raw class labels, 0 = void, gathered into every batch as "semantics" (n) int64."""
 
     def __init__(self, images, poses, directions, img_wh, batch_size=8192, patch_size=8,
                  ray_sampling_strategy="all_images_triang_patch", seed=0, corner_mode="reference", optimize_ext=False,
-                 depth=None, normals=None, normals_depth=None):
+                 depth=None, normals=None, normals_depth=None, semantics=None):
         if ray_sampling_strategy not in STRATEGIES:
             raise ValueError(f"ray_sampling_strategy {ray_sampling_strategy!r} is not implemented on the device; "
                              f"one of {STRATEGIES}")
@@ -114,7 +129,7 @@ class DeviceRayDataset:
             raise ValueError(f"corner_mode {corner_mode!r}; one of {sorted(CORNER_MODES)}")
         planes = {k: t for k, t in zip(LABEL_PLANES, (depth, normals, normals_depth)) if t is not None}
         for t, name in ((images, "images"), (poses, "poses"), (directions, "directions")) + tuple(
-                (t, k) for k, t in planes.items()):
+                (t, k) for k, t in planes.items()) + (((semantics, "semantics"),) if semantics is not None else ()):
             if not isinstance(t, torch.Tensor):
                 raise RuntimeError(f"{name} must be a CUDA tensor")
         W, H = int(img_wh[0]), int(img_wh[1])
@@ -143,6 +158,13 @@ class DeviceRayDataset:
                 planes[k] = t = t.reshape(shape)
             if tuple(t.shape) != shape:
                 raise ValueError(f"{k} must be {shape} for img_wh {(W, H)} (got {tuple(t.shape)})")
+        if semantics is not None:
+            if semantics.dtype not in _SEMANTICS_DTYPES:
+                raise RuntimeError(f"semantics must be torch.uint8, torch.int32 or torch.int64 (got {semantics.dtype})")
+            if tuple(semantics.shape) == (V, H, W):
+                semantics = semantics.reshape(V, H * W)
+            if tuple(semantics.shape) != (V, H * W):
+                raise ValueError(f"semantics must be {(V, H * W)} for img_wh {(W, H)} (got {tuple(semantics.shape)})")
         patch_size, batch_size = int(patch_size), int(batch_size)
         if patch_size < 1 or patch_size > min(H, W):
             raise ValueError(f"patch_size {patch_size} does not fit a {W}x{H} image")
@@ -157,8 +179,13 @@ class DeviceRayDataset:
         for k, t in planes.items():
             if t.device != images.device:
                 raise RuntimeError(f"{k} must be on the device of images")
+        if semantics is not None:
+            _lib.check_input(semantics, "semantics")
+            if semantics.device != images.device:
+                raise RuntimeError("semantics must be on the device of images")
         self.images, self.poses, self.directions = images, poses, directions
         self.planes = planes  # the label planes that were given, by name
+        self.semantics = semantics  # the integer label plane, or None (not one of LABEL_PLANES: another gather)
         self.H, self.W, self.n_images = H, W, V
         self.batch_size, self.patch_size = batch_size, patch_size
         self.n_patches = batch_size // (patch_size * patch_size)
@@ -176,7 +203,7 @@ class DeviceRayDataset:
 
     def buffers(self, n_rays=None, labels=True):
         """Preallocated outputs of batch(out=...): the static batch buffers of a captured step, with
-        one buffer per label plane of the dataset unless labels is False."""
+        one buffer per label plane of the dataset (the semantics included) unless labels is False."""
         n = self.batch_size if n_rays is None else n_rays
         f = dict(dtype=torch.float32, device=self.device)
         i = dict(dtype=torch.int64, device=self.device)
@@ -184,6 +211,8 @@ class DeviceRayDataset:
                "img_idxs": torch.empty(n, **i), "pix_idxs": torch.empty(n, **i)}
         for k in (self.planes if labels else ()):
             out[k] = torch.empty((n,) if k == "depth" else (n, 3), **f)
+        if labels and self.semantics is not None:
+            out["semantics"] = torch.empty(n, **i)
         return out
 
     def _rays(self, img_idxs, pix_idxs, out):
@@ -201,7 +230,8 @@ class DeviceRayDataset:
         """The batch of `step` (an int or a device int64 scalar) as the dict Trainer.step and NeRFMTLoss
         take.  out: buffers() to write into (nothing is allocated: capturable); seed: overrides the
         dataset's (data-parallel ranks draw with seed + rank).  No host read either way.  The label
-        planes the dataset holds come with it under "depth" (n), "normals", "normals_depth" (n, 3)."""
+        planes the dataset holds come with it under "depth" (n), "normals", "normals_depth" (n, 3),
+        "semantics" (n) int64."""
         out = self.buffers() if out is None else out
         batch_draw(self.seed if seed is None else seed, step, self.n_images, self.H, self.W, self.patch_size,
                    self.n_patches, self.same_image, self.corner_mode, out["img_idxs"], out["pix_idxs"])
@@ -212,6 +242,9 @@ class DeviceRayDataset:
         if self.planes:  # (one launch for all of them)
             batch_labels_fw(out["img_idxs"], out["pix_idxs"], self.planes, out)
             batch.update((k, out[k]) for k in self.planes)
+        if self.semantics is not None:
+            batch_semantics_fw(out["img_idxs"], out["pix_idxs"], self.semantics, out["semantics"])
+            batch["semantics"] = out["semantics"]
         return batch
 
     def image_rays(self, v):

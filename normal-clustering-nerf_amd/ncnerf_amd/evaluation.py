@@ -8,7 +8,8 @@
   manhattan_frame                   <- train_nerf.py:503-513 (closest +-centroids, projection on SO(3))
   evaluate_views                    <- validation_step + validation_epoch_end: render, PSNR, normals
                                        per view, ONE clustering over all views, the frame; on request
-                                       val_metrics.update / compute (metrics.ViewMetrics)
+                                       val_metrics.update / compute (metrics.ViewMetrics), the norm_nn
+                                       and semantic metrics included where the model has the heads
 
 The k-means is the restatement of faiss's Clustering::train that oracle/losses_ref.py:spherical_kmeans
 states (faiss itself stays parity-unpinned, as for the training loss); the normals never leave the
@@ -199,7 +200,7 @@ def manhattan_frame(centrs_new, R_ref=None):
 
 
 def evaluate_views(model, poses, ray_dirs_cc, img_wh, rgb_gt=None, K=30, niter=30, t_similar=0.99, R_ref=None,
-                   depth_gt=None, normals_gt=None, metrics=False, **render_kwargs):
+                   depth_gt=None, normals_gt=None, metrics=False, sem_gt=None, **render_kwargs):
     """validation_step over every pose + validation_epoch_end's frame extraction.
 
     poses (V,3,4) or (V,4,4) camera-to-world, ray_dirs_cc (H*W,3), img_wh = (W, H), rgb_gt (V,H*W,3)
@@ -216,14 +217,31 @@ def evaluate_views(model, poses, ray_dirs_cc, img_wh, rgb_gt=None, K=30, niter=3
     SSIMs; the depth errors with depth_gt; the angular errors of the depth-image normals with
     normals_gt), which needs rgb_gt, and the result gains "metrics" (ViewMetrics.compute()'s log
     keys) and "per_view" (one {column: value} per view).  The PSNRs are then column 0 of the rows, so
-    there is still one device-to-host copy outside the renderer and the clustering."""
-    from .metrics import COLUMNS, ViewMetrics
+    there is still one device-to-host copy outside the renderer and the clustering.
+
+    With normals_gt and a model with the normal head (model.pred_norm: the reference's `pred_norm_nn and
+    load_norm_gt`) the rendered `norm_nn` is scored too: "metrics" gains norm_nn/ang_err_* and every
+    "per_view" entry the columns nn_ang_mean, nn_ang_median, nn_ang_mean_min, nn_ang_median_min,
+    nn_norm_counted.  With sem_gt (V,H*W) or (V,H,W), raw integer labels with 0 = void, the rendered
+    `sem` logits are counted into one confusion matrix over the views (ncn_sem_confusion reads the slice
+    of the render buffer in place): "metrics" gains sem/miou, sem/miou_valid_cls, sem/total_acc,
+    sem/cls_avg_acc, and the result "sem_ious" (the per-class list) and "conf_mat" (K,K int64, on the
+    device).  sem_gt needs a model with the semantic head (model.pred_sem) and n_sem_cls among the
+    render arguments: ValueError otherwise.  The host copy stays the one."""
+    from .metrics import COLUMNS, NN_COLUMNS, ViewMetrics
     from .rendering import render
     vm = None
-    if metrics or depth_gt is not None or normals_gt is not None:
+    if sem_gt is not None:
+        if not getattr(model, "pred_sem", False):
+            raise ValueError("evaluate_views: sem_gt needs a model with the semantic head (pred_sem=True)")
+        if render_kwargs.get("n_sem_cls") is None:
+            raise ValueError("evaluate_views: sem_gt needs n_sem_cls among the render arguments")
+    if metrics or depth_gt is not None or normals_gt is not None or sem_gt is not None:
         if rgb_gt is None:
             raise ValueError("evaluate_views: the metrics need rgb_gt")
-        vm = ViewMetrics(eval_depth=depth_gt is not None, norm_gt=normals_gt is not None)
+        vm = ViewMetrics(eval_depth=depth_gt is not None, norm_gt=normals_gt is not None,
+                         pred_norm_nn=bool(getattr(model, "pred_norm", False)), eval_sem=sem_gt is not None,
+                         n_sem_cls=render_kwargs.get("n_sem_cls"))
     W, H = int(img_wh[0]), int(img_wh[1])
     poses = poses.float()
     dirs = ray_dirs_cc.float().contiguous()
@@ -250,15 +268,28 @@ def evaluate_views(model, poses, ray_dirs_cc, img_wh, rgb_gt=None, K=30, niter=3
                     target["depth"] = depth_gt[v].reshape(-1).to(rgb).contiguous()
                 if normals_gt is not None:
                     target["normals"] = normals_gt[v].reshape(-1, 3).to(rgb).contiguous()
+                if vm.pred_norm_nn:
+                    preds["norm_nn"] = res["norm_nn"].reshape(-1, 3)
+                if sem_gt is not None:
+                    preds["sem"] = res["sem"]  # (a channel slice of the render buffer: read in place)
+                    target["semantics"] = sem_gt[v].reshape(-1).to(rgb.device)
                 vm.update(preds, target, H, W)
             elif rgb_gt is not None:
                 mse = ((res["rgb"].reshape(-1, 3) - rgb_gt[v].reshape(-1, 3).to(res["rgb"])) ** 2).mean()
                 psnr.append(-10.0 * torch.log10(mse))
         extra = {}
         if vm is not None:
-            rows = vm.rows().tolist()  # the one copy: V x 12 scalars
+            # the one copy: V x 12 scalars (+ V x 5 of the norm_nn tag, + the 4 + K semantic scores)
+            rows, nn_rows, sem = vm.unpack(vm.packed().tolist())
             psnr = [r[0] for r in rows]
-            extra = {"metrics": vm.logs(rows), "per_view": [dict(zip(COLUMNS, r)) for r in rows]}
+            per_view = [dict(zip(COLUMNS, r)) for r in rows]
+            if nn_rows is not None:
+                for d, r in zip(per_view, nn_rows):
+                    d.update(zip(("nn_" + c for c in NN_COLUMNS), r))
+            extra = {"metrics": vm.logs(rows, nn_rows, sem), "per_view": per_view}
+            if sem is not None:
+                extra["sem_ious"] = list(sem[4:])
+                extra["conf_mat"] = vm.sem.conf_mat
         else:
             psnr = torch.stack(psnr).tolist() if psnr else []
         labels, _, cents = normals_clustering(normals, K=K, niter=niter, t_similar=t_similar, merge_clusters=True,
