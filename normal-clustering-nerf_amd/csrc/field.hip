@@ -19,11 +19,13 @@
 // Operand precision is a template parameter: fp16 (tcnn's FullyFusedMLP precision) or bf16
 // (config #3); fp32 hash table + fp32 trilinear interpolation, fp32 accumulation either way.
 // One translation unit on purpose: the device code is in the field_*.h headers, one per stage (DESIGN.md,
-// source map), and this file holds the launchers and the C ABI.
+// source map), and this file holds the launchers and the C ABI.  (One instantiation of the MLP backward
+// lives beside it, in field_rgb_din.hip, which says why; field_bwd_launch.h is what the two share.)
 #include <algorithm>
 #include <cstring>
 #include "field_fwd.h"
 #include "field_bwd_mlp.h"
+#include "field_bwd_launch.h"
 #include "field_scatter.h"
 #include "field_bwd_dx.h"
 
@@ -52,44 +54,8 @@ static int fwd_grid(int64_t n) {
 }  // namespace ncn
 using namespace ncn;
 
-// The fp16 / bf16 ladder: f gets a tag whose ::type is the operand type of `precision` (checked by the caller).
-template <typename T> struct Operand { typedef T type; };
-template <typename F>
-static void with_operand(int precision, F&& f) {
-    if (precision == NCN_PREC_F16) f(Operand<_Float16>{});
-    else f(Operand<__bf16>{});
-}
-
-// The argument checks of the three MLP-backward entries in their common order: the precision, the
-// entry's own requirements (`own`: the message of the first one violated, or null), the alignment
-// (`part_entry`: with dh_stash), level_max, and the entry's last requirement (`last`, as `own`).
-static int bwd_mlp_check(const char* name, int precision, const char* own, const void* dE_ws, const void* enc,
-                         const void* wp, const void* stash, bool part_entry, const void* level_max, const char* last) {
-    NCN_REQUIRE(precision == NCN_PREC_F16 || precision == NCN_PREC_BF16, hipErrorInvalidValue,
-                "%s: precision must be NCN_PREC_F16 or NCN_PREC_BF16", name);
-    NCN_REQUIRE(!own, hipErrorInvalidValue, "%s: %s", name, own);
-    NCN_REQUIRE((((uintptr_t)dE_ws | (uintptr_t)enc | (uintptr_t)wp | (uintptr_t)stash) & 15) == 0, hipErrorInvalidValue,
-                "%s: dE_ws / enc_cache / weights_packed%s must be 16-byte aligned", name, part_entry ? " / dh_stash" : "");
-    NCN_REQUIRE(level_max != nullptr, hipErrorInvalidValue, "%s: level_max workspace required", name);
-    NCN_REQUIRE(!last, hipErrorInvalidValue, "%s: %s", name, last);
-    return 0;
-}
 static const char* xyzs_unaligned(const float* xyzs) {
     return ((uintptr_t)xyzs & 15) == 0 ? nullptr : "xyzs must be 16-byte aligned";
-}
-
-template <int PART, bool DIN = false>
-static void launch_bwd_part(int precision, int nb, hipStream_t st, const float* xyzs, const float* dirs, int64_t n,
-                            const int32_t* n_dev, const uint16_t* wp, const uint16_t* enc, const float* dsig,
-                            const float* drgb, const float* loss_scale, float* dE_ws, float* slab, float* level_max,
-                            const int32_t* order, const float* dsig2, float* stash, const float* w_master = nullptr,
-                            float* dL_ddirs = nullptr) {
-    with_operand(precision, [&](auto op) {
-        typedef typename decltype(op)::type T;
-        hipLaunchKernelGGL((field_bwd_kernel<T, PART, DIN>), dim3(nb), dim3(BWD_THREADS), 0, st, dirs, n, n_dev, wp,
-                           (const typename Mfma<T>::v8*)enc, dsig, drgb, loss_scale, dE_ws, slab, level_max, order, dsig2,
-                           stash, xyzs, w_master, dL_ddirs);
-    });
 }
 
 // (ncn_field_reduce_wgrad / _parts; `name` for the launch check's message)

@@ -93,8 +93,9 @@ __device__ __forceinline__ float lmax_upd(float m, float a, float b) {  // non-f
 template <int PART> constexpr int x_count() { return PART == BWD_SIGMA ? N_XFRAG - XA2 : N_XFRAG; }
 template <int PART> constexpr int x_origin() { return PART == BWD_SIGMA ? XA2 : 0; }
 
-// (DIN, the one-pass form only) the direction gradient's operands: W3's three direction columns
-// rounded to T in LDS ([k][64 rows]), the processing order and the output (n, 3) in sample order
+// (DIN: the one-pass form, or the split backward's rgb part) the direction gradient's operands:
+// W3's three direction columns rounded to T in LDS ([k][64 rows]), the processing order and the
+// output (n, 3) in sample order
 template <typename T>
 struct DinCtx {
     const T* w3d;
@@ -422,7 +423,7 @@ __device__ __forceinline__ void field_bwd_body(
     float* __restrict__ slab, float* __restrict__ level_max, const int32_t* __restrict__ order,
     const float* __restrict__ dL_dsig2, float* __restrict__ stash, const float* __restrict__ xyzs,
     const float* __restrict__ w_master, float* __restrict__ dL_ddirs) {
-    static_assert(!DIN || PART == BWD_ALL, "the direction gradient leaves the one-pass form only");
+    static_assert(!DIN || (PART & BWD_RGB) != 0, "the direction gradient leaves with the rgb_net path, not the sigma part");
     typedef typename Mfma<T>::v4 v4;
     if (rgb_on && *rgb_on == 0.f) dL_drgb = nullptr;  // (uniform; bwd_load then leaves dr0..2 at zero)
     // AMP loss scale (GradScaler of the reference's precision=16 run) times tcnn's fp16 module loss
@@ -544,9 +545,10 @@ __device__ __forceinline__ void field_bwd_body(
         SG_TNOW(g3);
         if constexpr (DIN) {
             // The transposed LDS reads of phase 2 must run with EXEC all ones (x_get): the group count
-            // and the wave index are uniform, but this instantiation's register allocation keeps them
-            // in vector registers, and a zero half of x_pair then becomes a read under EXEC = 0, which
-            // returns the stale tile.  As scalars they are branches again.
+            // and the wave index are uniform, but the DIN instantiations' register allocation (the
+            // one-pass form's; the rgb part's takes the same operands) keeps them in vector registers,
+            // and a zero half of x_pair then becomes a read under EXEC = 0, which returns the stale
+            // tile.  As scalars they are branches again.
             bwd_dw<T, PART>(X, __builtin_amdgcn_readfirstlane(ng), __builtin_amdgcn_readfirstlane(wid), lane, acc);
         } else
             bwd_dw<T, PART>(X, ng, wid, lane, acc);

@@ -2,15 +2,17 @@
 validation metrics in include/ncnerf_metrics.h, for the geometry supervision (the depth, GT-normal
 and RegNeRF loss terms, the label gather) in include/ncnerf_geom.h, for the isosurface extraction
 in include/ncnerf_mesh.h, for the semantic / normal heads and the compositing of their channels in
-include/ncnerf_heads.h, and for the semantic metrics and the integer label gather in include/ncnerf_sem.h.
+include/ncnerf_heads.h, for the semantic metrics and the integer label gather in include/ncnerf_sem.h,
+and for the direction gradient of the split backward in include/ncnerf_input_grad.h.
 
 This is the only place Python talks to the HIP kernels.  There is NO CPU fallback: if the library
 is missing, or a kernel is called with a CPU tensor, the call raises.  Tensors are passed as raw
 device pointers and sizes, on torch's *current* HIP stream (never the legacy default stream).
 
 The headers are the single statement of the ABI: parsed at import (ncnerf.h and ncnerf_metrics.h
-into the table ABI, ncnerf_geom.h, ncnerf_mesh.h, ncnerf_heads.h and ncnerf_sem.h into tables of their
-own, GEOM_ABI, MESH_ABI, HEADS_ABI and SEM_ABI), they give every argtypes / restype, and `call`
+into the table ABI, ncnerf_geom.h, ncnerf_mesh.h, ncnerf_heads.h, ncnerf_sem.h and ncnerf_input_grad.h
+into tables of their own, GEOM_ABI, MESH_ABI, HEADS_ABI, SEM_ABI and INPUT_GRAD_ABI), they give every
+argtypes / restype, and `call`
 marshals plain arguments against them (see `marshal`) before anything is launched.
 """
 import ctypes
@@ -28,6 +30,7 @@ GEOM_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ncnerf_geom.h")  
 MESH_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ncnerf_mesh.h")  # same grammar, all `int`
 HEADS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ncnerf_heads.h")  # same grammar, all `int`
 SEM_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ncnerf_sem.h")  # same grammar, all `int`
+INPUT_GRAD_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ncnerf_input_grad.h")  # same grammar, all `int`
 
 P = ctypes.c_void_p
 I64 = ctypes.c_int64
@@ -189,6 +192,23 @@ def _parse_sem_header(tables):
     return sem
 
 
+def _read_input_grad_header():
+    try:
+        return open(INPUT_GRAD_HEADER_PATH).read()
+    except OSError as e:
+        raise NcnError(f"include/ncnerf_input_grad.h not found at {INPUT_GRAD_HEADER_PATH}: the binding of the split "
+                       f"backward's direction gradient is derived from it ({e})") from None
+
+
+def _parse_input_grad_header(tables):
+    """The seventh header's table; a name that one of `tables` (the other headers') declares too is an error."""
+    grad = parse_header(_read_input_grad_header())
+    for name in grad:
+        if any(name in t for t in tables):
+            raise NcnError(f"{name} is declared in include/ncnerf_input_grad.h and in another header of include/")
+    return grad
+
+
 ABI = _parse_headers()
 GEOM_ABI = _parse_geom_header(ABI)
 TABLES = (ABI, GEOM_ABI)
@@ -197,12 +217,14 @@ ALL_TABLES = TABLES + (MESH_ABI,)  # what is bound beside the heads; TABLES stay
 HEADS_ABI = _parse_heads_header(ALL_TABLES)
 BOUND_TABLES = ALL_TABLES + (HEADS_ABI,)  # the tables bound before the semantic metrics came
 SEM_ABI = _parse_sem_header(BOUND_TABLES)
-LOADED_TABLES = BOUND_TABLES + (SEM_ABI,)  # every table lib() binds
+LOADED_TABLES = BOUND_TABLES + (SEM_ABI,)  # the tables bound before the split backward's direction gradient came
+INPUT_GRAD_ABI = _parse_input_grad_header(LOADED_TABLES)
+EVERY_TABLE = LOADED_TABLES + (INPUT_GRAD_ABI,)  # every table lib() binds
 
 
 def declaration(name):
     """(restype, parameters) of an entry point, whichever header declares it."""
-    for table in LOADED_TABLES:
+    for table in EVERY_TABLE:
         decl = table.get(name)
         if decl is not None:
             return decl
@@ -211,7 +233,7 @@ def declaration(name):
 
 # name -> argtypes (stream last), as ctypes sees them
 SIGNATURES = dict((name, [P if kind == "ptr" else _SCALARS[kind] for kind, _, _ in params])
-                  for table in LOADED_TABLES for name, (_, params) in table.items())
+                  for table in EVERY_TABLE for name, (_, params) in table.items())
 
 _lib = None
 
@@ -232,7 +254,7 @@ def lib():
             raise NcnError(f"libncnerf.so not found at {LIB_PATH}: run __graft_entry__.build() "
                            f"(make -C normal-clustering-nerf_amd)")
         L = ctypes.CDLL(LIB_PATH)
-        for table in LOADED_TABLES:
+        for table in EVERY_TABLE:
             for name, (ret, _) in table.items():
                 fn = getattr(L, name)
                 fn.argtypes = SIGNATURES[name]
@@ -253,6 +275,11 @@ def heads_symbols():
 def sem_symbols():
     """The entry points of include/ncnerf_sem.h (bound by lib() like every other)."""
     return list(SEM_ABI)
+
+
+def input_grad_symbols():
+    """The entry points of include/ncnerf_input_grad.h (bound by lib() like every other)."""
+    return list(INPUT_GRAD_ABI)
 
 
 def mesh_symbols():
@@ -321,7 +348,7 @@ def _marshaller(name, params):
     return ns["marshal"], (n - 1, n) if _launches(params) else (n,)
 
 
-_PLANS = {name: _marshaller(name, params) for table in LOADED_TABLES for name, (_, params) in table.items()}
+_PLANS = {name: _marshaller(name, params) for table in EVERY_TABLE for name, (_, params) in table.items()}
 
 
 def marshal(name, args):

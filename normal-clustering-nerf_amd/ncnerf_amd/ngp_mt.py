@@ -30,7 +30,10 @@ sem_net / norm_net, tcnn FullyFusedMLP(16 -> 64 -> 64 -> K / 3) on the 16 sigma_
 appended to the flat buffers behind W5 (every existing offset stays), `forward` also returns 'sems'
 (N, K) / 'norms' (N, 3), and the backward runs the split MLP pass with each head's backward between
 its two parts: the head adds its dL/dh into the stash the sigma part consumes.  With both heads off
-every path is what it was.  Not with a head: sort_samples, input gradients (dL/dx, dL/dd).
+every path is what it was.  Input gradients with a head (the reference lists --pred_sem beside
+--optimize_ext): dL/dd leaves the rgb part (ncn_field_bwd_mlp_rgb_din; the heads read h, never d),
+dL/dx is ncn_field_bwd_dx over the sigma part's encoding gradient, which carries the heads' dL/dh.
+Not with a head: sort_samples.
 
 Not provided (off in every reference config, hyperparameters.py:26-30): rgb_act='None' exposure
 tonemappers.
@@ -112,7 +115,9 @@ class _FieldFunction(torch.autograd.Function):
     w.r.t. the inputs x and d (camera pose refinement, density normals): dL/dd leaves the MLP pass
     (ncn_field_bwd_mlp_din), dL/dx is a second hash-grid gather over the encoding gradient the MLP
     pass left in its workspace (ncn_field_bwd_dx).  With every parameter frozen only the MLP pass
-    and the input kernels run: no table scatter, no weight-gradient reduction, flat_grad untouched."""
+    and the input kernels run: no table scatter, no weight-gradient reduction, flat_grad untouched.
+    (A model with heads takes _FieldHeadsFunction, which gives the same input gradients out of the
+    split backward.)"""
 
     @staticmethod
     def forward(ctx, x, d, table, w_sigma, w_rgb, model, mode, n_dev=None):
@@ -187,13 +192,19 @@ class _FieldHeadsFunction(torch.autograd.Function):
     cache -> (sigmas, rgbs, one (N, n_out) output per head in the model's head order).  Backward:
     ncn_field_bwd_mlp_part part 1 (rgb_net, its dL/dh into the stash), ncn_head_bwd per head (weight
     gradients; its dL/dh added into the stash), part 2 (TruncExp, sigma_net, the encoding gradient),
-    the table scatter and the weight-gradient reductions.  No input gradients."""
+    the table scatter and the weight-gradient reductions.
+
+    Differentiable w.r.t. x and d as _FieldFunction is (camera pose refinement with the semantic /
+    normal terms on): dL/dd leaves part 1 (ncn_field_bwd_mlp_rgb_din: the heads read h, never d),
+    dL/dx is ncn_field_bwd_dx over the encoding gradient part 2 left, which carries rgb_net's, every
+    head's and TruncExp's dL/dh through sigma_net.  With every parameter frozen only the MLP parts,
+    the head backwards and the input kernels run: no table scatter, no weight-gradient reduction
+    (the heads' included), flat_grad untouched."""
 
     @staticmethod
     def forward(ctx, x, d, n_dev, model, *params):
-        need_grad = any(ctx.needs_input_grad[4:])
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            raise NotImplementedError("input gradients (dL/dx, dL/dd) are not available with a pred_sem / pred_norm head")
+        need_in = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        need_grad = need_in or any(ctx.needs_input_grad[4:])
         # (the encoding cache is the heads' input: needed as scratch at inference too)
         sigmas, rgbs, enc, packed, _ = model._field_fwd(x, d, n_dev, 0, True)
         n = x.shape[0]
@@ -204,41 +215,56 @@ class _FieldHeadsFunction(torch.autograd.Function):
                 call("ncn_head_fwd", enc, n, n_dev, packed, model._head_packed[name], n_out, model._prec, o)
             outs.append(o)
         if need_grad:
-            ctx.save_for_backward(x, d, enc, packed, n_dev, *[model._head_packed[h[0]] for h in model._heads])
+            ctx.save_for_backward(x, d, enc, packed, n_dev, model.xyz_encoder.params if need_in else None,
+                                  *[model._head_packed[h[0]] for h in model._heads])
             ctx.model = model
         ctx.set_materialize_grads(False)
         return (sigmas, rgbs) + tuple(outs)
 
     @staticmethod
     def backward(ctx, dL_dsigmas, dL_drgbs, *dL_dheads):
-        x, d, enc, packed, n_dev, *head_packed = ctx.saved_tensors
+        x, d, enc, packed, n_dev, table, *head_packed = ctx.saved_tensors
         model = ctx.model
         n, dev = x.shape[0], x.device
-        none = (None,) * (4 + 3 + len(model._heads))
+        need_x, need_d = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_param = any(ctx.needs_input_grad[4:])
+        none = (None,) * (2 + 3 + len(model._heads))
         if n == 0:
-            return none
+            return (torch.zeros_like(x) if need_x else None, torch.zeros_like(d) if need_d else None) + none
         L = _lib.lib()
         c = lambda t: None if t is None else t.contiguous().float()
         scale = model._bwd_loss_scale()
-        g_table, g_w = model._grad_views()
+        g_table, g_w = model._grad_views() if need_param else (None, None)
         nb = (int(L.ncn_field_bwd_part_blocks(n, 1)), int(L.ncn_field_bwd_part_blocks(n, 2)))
         slab = torch.empty(max(nb) * N_W, dtype=torch.float32, device=dev)
         dE_ws = torch.empty(int(L.ncn_field_bwd_dE_floats(n)), dtype=torch.float32, device=dev)
         stash = torch.empty(int(L.ncn_field_bwd_stash_floats(n)), dtype=torch.float32, device=dev)
         lmax = model._level_max()
-        call("ncn_field_bwd_mlp_part", x, d, n, n_dev, None, packed, model._prec, enc, None, None, c(dL_drgbs), scale,
-             1, nb[0], slab, dE_ws, lmax, stash)
+        dL_dx = dL_dd = None
+        if need_d:
+            dL_dd = torch.empty(n, 3, dtype=torch.float32, device=dev)  # (the kernel zeroes rows >= *n_dev)
+            call("ncn_field_bwd_mlp_rgb_din", x, d, n, n_dev, None, packed, model._prec, enc, c(dL_drgbs), scale, nb[0],
+                 slab, dE_ws, lmax, stash, model._flat[model._n_table:], dL_dd)
+        else:
+            call("ncn_field_bwd_mlp_part", x, d, n, n_dev, None, packed, model._prec, enc, None, None, c(dL_drgbs),
+                 scale, 1, nb[0], slab, dE_ws, lmax, stash)
         nbh = int(L.ncn_head_bwd_blocks(n))
         for (name, n_out, off, n_w), hp, g in zip(model._heads, head_packed, dL_dheads):
             if g is None:
                 continue
             hslab = torch.empty(nbh * n_w, dtype=torch.float32, device=dev)
             call("ncn_head_bwd", enc, n, n_dev, packed, hp, n_out, model._prec, c(g), scale, hslab, stash)
-            call("ncn_head_reduce_wgrad", hslab, nbh, n_w, model._flat_grad[off:off + n_w])
+            if need_param:
+                call("ncn_head_reduce_wgrad", hslab, nbh, n_w, model._flat_grad[off:off + n_w])
         call("ncn_field_bwd_mlp_part", x, d, n, n_dev, None, packed, model._prec, enc, c(dL_dsigmas), None, None, scale,
              2, nb[1], slab, dE_ws, lmax, stash)
-        model._scatter(x, n, n_dev, None, dE_ws, lmax, g_table, wgrad=(slab, nb[1], nb[0], g_w))
-        return none
+        if need_param:
+            model._scatter(x, n, n_dev, None, dE_ws, lmax, g_table, wgrad=(slab, nb[1], nb[0], g_w))
+        if need_x:
+            dL_dx = torch.empty(n, 3, dtype=torch.float32, device=dev)  # (the kernel zeroes rows >= *n_dev)
+            call("ncn_field_bwd_dx", x, n, n_dev, None, table, model._levels_ptr, model._xyz_min, model._xyz_extent,
+                 dE_ws, dL_dx)
+        return (dL_dx, dL_dd) + none
 
 
 class NGPMT(nn.Module):
