@@ -217,6 +217,19 @@ __global__ __launch_bounds__(256) void adam_apply_kernel(float* __restrict__ p, 
         const float denom = sqrtf(vi / bc2) + eps;
         pi = pi - lr * ((mi / bc1) / denom + wd * pi);
     };
+    // The scalar tail (the last n % 4 parameters): upd with the fused operations the float4 body
+    // compiles to written out and contraction off.  Left to the compiler, the tail of the packed
+    // instances was contracted differently from the plain instance's, and ncn_adam_step_packed's
+    // last parameters came out one ulp off ncn_adam_step's (tests/test_gpu_guard_bands.py).  (Written
+    // out in the float4 body too, the same operations are scheduled ~1 us slower.)
+    auto upd_tail = [&](float& pi, float gr, float& mi, float& vi, float wd) {
+#pragma clang fp contract(off)
+        const float gi = gr * cf;
+        mi = fmaf(b1, mi, (1.f - b1) * gi);
+        vi = fmaf(b2, vi, ((1.f - b2) * gi) * gi);
+        const float denom = sqrtf(vi / bc2) + eps;
+        pi = fmaf(-lr, fmaf(wd, pi, (mi / bc1) / denom), pi);
+    };
     const int64_t n4 = n / 4, tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nth = (int64_t)gridDim.x * 256;
 #pragma unroll 2
     for (int64_t i = tid; i < n4; i += nth) {
@@ -242,7 +255,7 @@ __global__ __launch_bounds__(256) void adam_apply_kernel(float* __restrict__ p, 
             ((float4*)g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     for (int64_t i = 4 * n4 + tid; i < n; i += nth) {
-        upd(p[i], g[i], m[i], v[i], i < n0 ? wd0 : wd1);
+        upd_tail(p[i], g[i], m[i], v[i], i < n0 ? wd0 : wd1);
         adam_pack1<PK>(i, p[i], pinv, poff, n, packed);
         if (ZERO) g[i] = 0.f;
     }
