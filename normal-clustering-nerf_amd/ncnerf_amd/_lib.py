@@ -1,19 +1,16 @@
-"""ctypes binding of libncnerf.so, derived from the C ABI declared in include/ncnerf.h, for the
-validation metrics in include/ncnerf_metrics.h, for the geometry supervision (the depth, GT-normal
-and RegNeRF loss terms, the label gather) in include/ncnerf_geom.h, for the isosurface extraction
-in include/ncnerf_mesh.h, for the semantic / normal heads and the compositing of their channels in
-include/ncnerf_heads.h, for the semantic metrics and the integer label gather in include/ncnerf_sem.h,
-and for the direction gradient of the split backward in include/ncnerf_input_grad.h.
+"""ctypes binding of libncnerf.so, derived from the C ABI declared in the headers of include/ that
+HEADERS lists.
 
 This is the only place Python talks to the HIP kernels.  There is NO CPU fallback: if the library
 is missing, or a kernel is called with a CPU tensor, the call raises.  Tensors are passed as raw
 device pointers and sizes, on torch's *current* HIP stream (never the legacy default stream).
 
-The headers are the single statement of the ABI: parsed at import (ncnerf.h and ncnerf_metrics.h
-into the table ABI, ncnerf_geom.h, ncnerf_mesh.h, ncnerf_heads.h, ncnerf_sem.h and ncnerf_input_grad.h
-into tables of their own, GEOM_ABI, MESH_ABI, HEADS_ABI, SEM_ABI and INPUT_GRAD_ABI), they give every
-argtypes / restype, and `call`
-marshals plain arguments against them (see `marshal`) before anything is launched.
+The headers are the single statement of the ABI, functions and constants: parsed at import in one
+pass (`load_headers`) into ABI (every entry point's restype and parameters), HEADER_OF (the header a
+name comes from) and CONSTANTS (every `#define NCN_<NAME> <literal>`; the Python modules look their
+values up here instead of retyping them).  ABI gives every argtypes / restype, and `call` marshals
+plain arguments against it (see `marshal`) before anything is launched.  A new header is one more
+entry of HEADERS.
 """
 import ctypes
 import operator
@@ -24,13 +21,19 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NCN_LIB_PATH") or os.path.join(_HERE, "libncnerf.so")  # (override: diagnostics)
-HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "ncnerf.h")
-METRICS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ncnerf_metrics.h")  # same grammar, all `int`
-GEOM_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ncnerf_geom.h")  # same grammar, all `int`
-MESH_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ncnerf_mesh.h")  # same grammar, all `int`
-HEADS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ncnerf_heads.h")  # same grammar, all `int`
-SEM_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ncnerf_sem.h")  # same grammar, all `int`
-INPUT_GRAD_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ncnerf_input_grad.h")  # same grammar, all `int`
+INCLUDE_DIR = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include")
+# The one place a header is named: file name -> what is derived from it (a missing file's message says
+# so).  All share ncnerf.h's grammar; the order is the order of ABI and of symbols().
+_DERIVED = {
+    "ncnerf.h": "the binding",
+    "ncnerf_metrics.h": "the binding of the validation metrics",
+    "ncnerf_geom.h": "the binding of the geometry supervision",
+    "ncnerf_mesh.h": "the binding of the isosurface extraction",
+    "ncnerf_heads.h": "the binding of the semantic / normal heads",
+    "ncnerf_sem.h": "the binding of the semantic metrics",
+    "ncnerf_input_grad.h": "the binding of the split backward's direction gradient",
+}
+HEADERS = tuple(_DERIVED)
 
 P = ctypes.c_void_p
 I64 = ctypes.c_int64
@@ -38,7 +41,6 @@ I32 = ctypes.c_int
 U32 = ctypes.c_uint32
 F32 = ctypes.c_float
 F64 = ctypes.c_double
-AMP_INIT_SCALE = 65536.0  # NCN_AMP_INIT_SCALE (include/ncnerf.h): torch GradScaler's init_scale
 U64 = ctypes.c_uint64
 
 
@@ -98,142 +100,87 @@ def parse_header(text):
     return out
 
 
-def _read_header():
+def header_path(name, include_dir=INCLUDE_DIR):
+    return os.path.join(include_dir, name)
+
+
+def read_header(name, include_dir=INCLUDE_DIR):
+    path = header_path(name, include_dir)
     try:
-        return open(HEADER_PATH).read()
+        return open(path).read()
     except OSError as e:
-        raise NcnError(f"include/ncnerf.h not found at {HEADER_PATH}: the binding is derived from it ({e})") from None
+        raise NcnError(f"include/{name} not found at {path}: {_DERIVED[name]} is derived from it ({e})") from None
 
 
-def _read_metrics_header():
-    try:
-        return open(METRICS_HEADER_PATH).read()
-    except OSError as e:
-        raise NcnError(f"include/ncnerf_metrics.h not found at {METRICS_HEADER_PATH}: the binding of the "
-                       f"validation metrics is derived from it ({e})") from None
+_DEFINE = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(NCN_\w+)(.*)$", flags=re.M)
+_INT = re.compile(r"[+-]?(?:0|[1-9]\d*)")
+_FLOAT = re.compile(r"[+-]?(?:(?:\d+\.\d*|\.\d+)(?:[eE][+-]?\d+)?|\d+[eE][+-]?\d+)[fF]?")
 
 
-def _read_geom_header():
-    try:
-        return open(GEOM_HEADER_PATH).read()
-    except OSError as e:
-        raise NcnError(f"include/ncnerf_geom.h not found at {GEOM_HEADER_PATH}: the binding of the geometry "
-                       f"supervision is derived from it ({e})") from None
+def parse_constants(text):
+    """({name: int | float}, [left-out names]) of a header's `#define NCN_<NAME> <body>` lines.  A body
+    that is a decimal integer or a C floating literal (an `f` suffix allowed) is a constant; any other
+    (an expression, a function-like macro, a brace list) is left out by name: nothing is evaluated."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants, left_out = {}, []
+    for name, body in _DEFINE.findall(text):
+        body = body.strip()
+        if name in constants or name in left_out:
+            raise ValueError(f"ncnerf.h grammar: {name} is defined twice")
+        if _INT.fullmatch(body):
+            constants[name] = int(body)
+        elif _FLOAT.fullmatch(body):
+            constants[name] = float(body.rstrip("fF"))
+        else:
+            left_out.append(name)
+    return constants, left_out
 
 
-def _parse_headers():
-    """One table from both headers; a name that both declare is an error."""
-    abi = parse_header(_read_header())
-    for name, decl in parse_header(_read_metrics_header()).items():
-        if name in abi:
-            raise NcnError(f"{name} is declared in both include/ncnerf.h and include/ncnerf_metrics.h")
-        abi[name] = decl
-    return abi
+def load_headers(include_dir=INCLUDE_DIR):
+    """(abi, header_of, constants, left_out) of every header of HEADERS under include_dir, in that order:
+    abi is {entry point: (restype, params)}, header_of {entry point or define: header file name}.  A name
+    that two headers declare or define is an NcnError naming both."""
+    abi, header_of, constants, left_out = {}, {}, {}, []
+    for header in HEADERS:
+        text = read_header(header, include_dir)
+        decls = parse_header(text)
+        values, opaque = parse_constants(text)
+        for name in (*decls, *values, *opaque):
+            if name in header_of:
+                raise NcnError(f"{name} is declared in include/{header} and in include/{header_of[name]}")
+            header_of[name] = header
+        abi.update(decls)
+        constants.update(values)
+        left_out += opaque
+    return abi, header_of, constants, tuple(left_out)
 
 
-def _parse_geom_header(abi):
-    """The third header's table; a name that `abi` (the first two headers) declares too is an error."""
-    geom = parse_header(_read_geom_header())
-    for name in geom:
-        if name in abi:
-            raise NcnError(f"{name} is declared in include/ncnerf_geom.h and in include/ncnerf.h or "
-                           f"include/ncnerf_metrics.h")
-    return geom
-
-
-def _read_mesh_header():
-    try:
-        return open(MESH_HEADER_PATH).read()
-    except OSError as e:
-        raise NcnError(f"include/ncnerf_mesh.h not found at {MESH_HEADER_PATH}: the binding of the isosurface "
-                       f"extraction is derived from it ({e})") from None
-
-
-def _parse_mesh_header(tables):
-    """The fourth header's table; a name that one of `tables` (the other headers') declares too is an error."""
-    mesh = parse_header(_read_mesh_header())
-    for name in mesh:
-        if any(name in t for t in tables):
-            raise NcnError(f"{name} is declared in include/ncnerf_mesh.h and in another header of include/")
-    return mesh
-
-
-def _read_heads_header():
-    try:
-        return open(HEADS_HEADER_PATH).read()
-    except OSError as e:
-        raise NcnError(f"include/ncnerf_heads.h not found at {HEADS_HEADER_PATH}: the binding of the semantic / "
-                       f"normal heads is derived from it ({e})") from None
-
-
-def _parse_heads_header(tables):
-    """The fifth header's table; a name that one of `tables` (the other headers') declares too is an error."""
-    heads = parse_header(_read_heads_header())
-    for name in heads:
-        if any(name in t for t in tables):
-            raise NcnError(f"{name} is declared in include/ncnerf_heads.h and in another header of include/")
-    return heads
-
-
-def _read_sem_header():
-    try:
-        return open(SEM_HEADER_PATH).read()
-    except OSError as e:
-        raise NcnError(f"include/ncnerf_sem.h not found at {SEM_HEADER_PATH}: the binding of the semantic metrics "
-                       f"is derived from it ({e})") from None
-
-
-def _parse_sem_header(tables):
-    """The sixth header's table; a name that one of `tables` (the other headers') declares too is an error."""
-    sem = parse_header(_read_sem_header())
-    for name in sem:
-        if any(name in t for t in tables):
-            raise NcnError(f"{name} is declared in include/ncnerf_sem.h and in another header of include/")
-    return sem
-
-
-def _read_input_grad_header():
-    try:
-        return open(INPUT_GRAD_HEADER_PATH).read()
-    except OSError as e:
-        raise NcnError(f"include/ncnerf_input_grad.h not found at {INPUT_GRAD_HEADER_PATH}: the binding of the split "
-                       f"backward's direction gradient is derived from it ({e})") from None
-
-
-def _parse_input_grad_header(tables):
-    """The seventh header's table; a name that one of `tables` (the other headers') declares too is an error."""
-    grad = parse_header(_read_input_grad_header())
-    for name in grad:
-        if any(name in t for t in tables):
-            raise NcnError(f"{name} is declared in include/ncnerf_input_grad.h and in another header of include/")
-    return grad
-
-
-ABI = _parse_headers()
-GEOM_ABI = _parse_geom_header(ABI)
-TABLES = (ABI, GEOM_ABI)
-MESH_ABI = _parse_mesh_header(TABLES)
-ALL_TABLES = TABLES + (MESH_ABI,)  # what is bound beside the heads; TABLES stays the training / validation surface
-HEADS_ABI = _parse_heads_header(ALL_TABLES)
-BOUND_TABLES = ALL_TABLES + (HEADS_ABI,)  # the tables bound before the semantic metrics came
-SEM_ABI = _parse_sem_header(BOUND_TABLES)
-LOADED_TABLES = BOUND_TABLES + (SEM_ABI,)  # the tables bound before the split backward's direction gradient came
-INPUT_GRAD_ABI = _parse_input_grad_header(LOADED_TABLES)
-EVERY_TABLE = LOADED_TABLES + (INPUT_GRAD_ABI,)  # every table lib() binds
+# ABI: every entry point's (restype, parameters); HEADER_OF: the header that declares (or defines) a name;
+# CONSTANTS: every `#define NCN_<NAME> <literal>`; NON_LITERAL_DEFINES: the defines that are no literal
+ABI, HEADER_OF, CONSTANTS, NON_LITERAL_DEFINES = load_headers()
+AMP_INIT_SCALE = CONSTANTS["NCN_AMP_INIT_SCALE"]  # torch GradScaler's init_scale
 
 
 def declaration(name):
     """(restype, parameters) of an entry point, whichever header declares it."""
-    for table in EVERY_TABLE:
-        decl = table.get(name)
-        if decl is not None:
-            return decl
-    raise KeyError(name)
+    return ABI[name]
+
+
+def symbols(header=None):
+    """The entry points of one header of HEADERS in declaration order, or of all of them in HEADERS order."""
+    if header is not None and header not in HEADERS:
+        raise KeyError(header)
+    return [name for name in ABI if header is None or HEADER_OF[name] == header]
+
+
+def exported_symbols():
+    """Every name libncnerf.so must export: all headers' entry points."""
+    return symbols()
 
 
 # name -> argtypes (stream last), as ctypes sees them
-SIGNATURES = dict((name, [P if kind == "ptr" else _SCALARS[kind] for kind, _, _ in params])
-                  for table in EVERY_TABLE for name, (_, params) in table.items())
+SIGNATURES = {name: [P if kind == "ptr" else _SCALARS[kind] for kind, _, _ in params]
+              for name, (_, params) in ABI.items()}
 
 _lib = None
 
@@ -254,37 +201,12 @@ def lib():
             raise NcnError(f"libncnerf.so not found at {LIB_PATH}: run __graft_entry__.build() "
                            f"(make -C normal-clustering-nerf_amd)")
         L = ctypes.CDLL(LIB_PATH)
-        for table in EVERY_TABLE:
-            for name, (ret, _) in table.items():
-                fn = getattr(L, name)
-                fn.argtypes = SIGNATURES[name]
-                fn.restype = _RESTYPES[ret]
+        for name, (ret, _) in ABI.items():
+            fn = getattr(L, name)
+            fn.argtypes = SIGNATURES[name]
+            fn.restype = _RESTYPES[ret]
         _lib = L
     return _lib
-
-
-def exported_symbols():
-    return [name for table in TABLES for name in table]
-
-
-def heads_symbols():
-    """The entry points of include/ncnerf_heads.h (bound by lib() like every other)."""
-    return list(HEADS_ABI)
-
-
-def sem_symbols():
-    """The entry points of include/ncnerf_sem.h (bound by lib() like every other)."""
-    return list(SEM_ABI)
-
-
-def input_grad_symbols():
-    """The entry points of include/ncnerf_input_grad.h (bound by lib() like every other)."""
-    return list(INPUT_GRAD_ABI)
-
-
-def mesh_symbols():
-    """The entry points of include/ncnerf_mesh.h (bound by lib() like every other)."""
-    return list(MESH_ABI)
 
 
 # ---- marshalling: one function per entry point, generated once from the header's parameters
@@ -348,7 +270,7 @@ def _marshaller(name, params):
     return ns["marshal"], (n - 1, n) if _launches(params) else (n,)
 
 
-_PLANS = {name: _marshaller(name, params) for table in EVERY_TABLE for name, (_, params) in table.items()}
+_PLANS = {name: _marshaller(name, params) for name, (_, params) in ABI.items()}
 
 
 def marshal(name, args):

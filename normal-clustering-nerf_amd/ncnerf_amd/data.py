@@ -24,8 +24,8 @@ from . import _lib
 from ._lib import call
 
 STRATEGIES = ("all_images_triang_patch", "same_image_triang_patch")
-CORNER_MODES = {"reference": 0, "grid": 1}  # NCN_CORNER_REFERENCE / NCN_CORNER_GRID
-_IMAGE_DTYPES = {torch.float32: 0, torch.uint8: 1}  # NCN_IMAGE_F32 / NCN_IMAGE_U8
+CORNER_MODES = {"reference": _lib.CONSTANTS["NCN_CORNER_REFERENCE"], "grid": _lib.CONSTANTS["NCN_CORNER_GRID"]}
+_IMAGE_DTYPES = {torch.float32: _lib.CONSTANTS["NCN_IMAGE_F32"], torch.uint8: _lib.CONSTANTS["NCN_IMAGE_U8"]}
 
 
 def patch_offsets(patch_size):

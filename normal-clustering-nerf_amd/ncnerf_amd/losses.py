@@ -192,7 +192,9 @@ def cluster_losses(norm_depth, K=K_CLUSTERS, niter=K_ITERS, seed=1234, t_similar
     return _ClusterLoss.apply(norm_depth, K, niter, seed, t_similar, _weights_arg(w))
 
 
-GEOM_DEPTH, GEOM_NORM_L1, GEOM_NORM_DOT, GEOM_REG = 1, 2, 4, 8  # NCN_GEOM_* (include/ncnerf_geom.h)
+_C = _lib.CONSTANTS  # the `terms` bits of include/ncnerf_geom.h: 1, 2, 4, 8
+GEOM_DEPTH, GEOM_NORM_L1, GEOM_NORM_DOT, GEOM_REG = (_C["NCN_GEOM_DEPTH"], _C["NCN_GEOM_NORM_L1"], _C["NCN_GEOM_NORM_DOT"],
+                                                     _C["NCN_GEOM_REG"])
 GEOM_KEYS = ("depth", "norm_D_L1", "norm_D_dot", "reg_depth")  # the node's four terms, in its order
 
 

@@ -20,7 +20,6 @@ No CPU fallback: a CPU tensor raises.
 """
 import collections
 import math
-import re
 
 import numpy as np
 import torch
@@ -29,15 +28,10 @@ from . import _lib
 from ._lib import call
 
 
-def _header_constants():
-    text = open(_lib.MESH_HEADER_PATH).read()
-    return {k: int(v) for k, v in re.findall(r"^#define NCN_MESH_(\w+) (\d+)$", text, flags=re.M)}
-
-
-_C = _header_constants()
-TILE = (_C["TILE_X"], _C["TILE_Y"], _C["TILE_Z"])  # points per workgroup of ncn_mesh_count, (x, y, z)
-SCAN_ELEMS = _C["SCAN_ELEMS"]  # elements per workgroup of ncn_mesh_scan
-SCAN_SWEEP = _C["SCAN_SWEEP"]  # block sums per sweep of its second pass
+_C = _lib.CONSTANTS
+TILE = (_C["NCN_MESH_TILE_X"], _C["NCN_MESH_TILE_Y"], _C["NCN_MESH_TILE_Z"])  # points per workgroup of ncn_mesh_count, (x, y, z)
+SCAN_ELEMS = _C["NCN_MESH_SCAN_ELEMS"]  # elements per workgroup of ncn_mesh_scan
+SCAN_SWEEP = _C["NCN_MESH_SCAN_SWEEP"]  # block sums per sweep of its second pass
 DEFAULT_ISO = 10.0  # a level, not a property of the method: pass the one that suits the scene's densities
 
 # (bitfield: uint8 CUDA tensor of grid_size**3 / 8 bytes, cascade 0 first; scale: the model's)

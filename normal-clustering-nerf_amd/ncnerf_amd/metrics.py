@@ -27,13 +27,13 @@ in counts[1] and otherwise skipped (torchmetrics raises or mis-indexes on it).
 """
 import torch
 
-from ._lib import call, check_input
+from ._lib import CONSTANTS, call, check_input
 
 COLUMNS = ("psnr", "ssim", "ssim_n", "ssim_n_sck", "depth_rmse", "depth_abs", "depth_counted",
            "ang_mean", "ang_median", "ang_mean_min", "ang_median_min", "norm_counted")
 NN_COLUMNS = ("ang_mean", "ang_median", "ang_mean_min", "ang_median_min", "norm_counted")  # the norm_nn tag's row
 SEM_KEYS = ("miou", "miou_valid_cls", "total_acc", "cls_avg_acc")  # ncn_sem_finalise's out[0:4]
-MAX_SEM_CLASSES = 64          # NCN_SEM_MAX_CLASSES
+MAX_SEM_CLASSES = CONSTANTS["NCN_SEM_MAX_CLASSES"]
 MIN_SIDE = 11                 # the 11x11 SSIM window
 # the workspace sizes include/ncnerf_metrics.h states
 _STREAM_THREADS, _STREAM_MAX_BLOCKS = 256, 1024

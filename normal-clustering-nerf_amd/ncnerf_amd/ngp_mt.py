@@ -46,21 +46,21 @@ from einops import rearrange
 from torch import nn
 
 from . import _lib, vren
-from ._lib import call
+from ._lib import CONSTANTS as _C, call  # (the header's #define NCN_* values)
 
 L_LEVELS, F_PER_LEVEL, LOG2_T, N_MIN = 16, 2, 19, 16  # ngp_mt.py:40
 # tcnn's padded shapes (ngp_mt.py:83-113 through tcnn.Network): sigma_net W1 (64,32) W2 (16,64);
 # rgb_net's 19 inputs padded to 32 with 1.0, 3 outputs padded to 16: W3 (64,32) W4 (64,64) W5 (16,64)
 MLP_SHAPES = ((64, 32), (16, 64), (64, 32), (64, 64), (16, 64))
 N_W = sum(o * i for o, i in MLP_SHAPES)  # NCN_FIELD_NW (10240: sigma_net 3072 + rgb_net 7168)
-PRECISIONS = {"fp16": 0, "bf16": 1}  # NCN_PREC_F16 / NCN_PREC_BF16
-N_PACKED_HALVES = 19456  # NCN_FIELD_PACKED_HALVES
-ENC_BYTES = 64  # NCN_ENC_BYTES_PER_SAMPLE
+PRECISIONS = {"fp16": _C["NCN_PREC_F16"], "bf16": _C["NCN_PREC_BF16"]}
+N_PACKED_HALVES = _C["NCN_FIELD_PACKED_HALVES"]
+ENC_BYTES = _C["NCN_ENC_BYTES_PER_SAMPLE"]
 SORT_MIN_SAMPLES = 8192  # training batches at least this large are evaluated in Morton-window order
 W_SIGMA = 64 * 32 + 16 * 64
 W_RGB = N_W - W_SIGMA
-HEAD_MAX_OUT = 48  # NCN_HEAD_MAX_OUT: three 16-row output tiles
-N_HEAD_PACKED_HALVES = 16384  # NCN_HEAD_PACKED_HALVES
+HEAD_MAX_OUT = _C["NCN_HEAD_MAX_OUT"]  # three 16-row output tiles
+N_HEAD_PACKED_HALVES = _C["NCN_HEAD_PACKED_HALVES"]
 
 
 def head_shapes(n_out):

@@ -14,31 +14,20 @@ import torch
 import geom_ref
 from ncnerf_amd import _lib
 from ncnerf_amd._lib import F32, I32, I64, P
+from test_abi import NAMES as ALL_NAMES, altered_headers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "geom_losses.npz")
-NAMES = {"ncn_geom_loss_fwd", "ncn_geom_loss_bwd", "ncn_batch_labels_fw"}
+HEADER = "ncnerf_geom.h"
+NAMES = ALL_NAMES[HEADER]
 CASES = ("depth", "norm", "norm_gtdepth", "reg_off", "reg_on", "all", "empty", "nan")
 
 
 # ---- the ABI ----
 def test_geom_header_parses_into_a_table_of_its_own():
-    assert _lib.GEOM_HEADER_PATH == os.path.join(ROOT, "include", "ncnerf_geom.h")
-    first = _lib.parse_header(open(_lib.HEADER_PATH).read())
-    second = _lib.parse_header(open(_lib.METRICS_HEADER_PATH).read())
-    third = _lib.parse_header(open(_lib.GEOM_HEADER_PATH).read())
-    assert set(third) == NAMES and _lib.GEOM_ABI == third
-    assert all(ret == "int" for ret, _ in third.values())
-    assert all(params[-1] == ("ptr", 0, "stream") for _, params in third.values())
-    # the first table stays the union of the other two headers
-    assert set(_lib.ABI) == set(first) | set(second) and not set(_lib.ABI) & NAMES
-    assert _lib.TABLES == (_lib.ABI, _lib.GEOM_ABI)
-    for name in NAMES:
-        assert _lib.declaration(name) == third[name] and len(_lib.SIGNATURES[name]) == len(third[name][1])
-    assert set(_lib.exported_symbols()) == set(_lib.ABI) | NAMES
-    # independent of the parser: every `ncn_name(` of the header outside its comments
-    text = re.sub(r"/\*.*?\*/", "", open(_lib.GEOM_HEADER_PATH).read(), flags=re.S)
-    assert set(re.findall(r"\b(ncn_\w+)\s*\(", text)) == NAMES
+    """(what every header shares, its names among it, is in test_abi.py)"""
+    assert _lib.header_path(HEADER) == os.path.join(ROOT, "include", HEADER)
+    assert set(_lib.symbols(HEADER)) == NAMES <= set(_lib.exported_symbols())
 
 
 def test_known_signatures():
@@ -47,7 +36,7 @@ def test_known_signatures():
     assert _lib.SIGNATURES["ncn_geom_loss_bwd"] == [P, P, I64, P, P, P, P, P, I64, P, P, I32, F32, F32, F32, P, P, P, P,
                                                     P]
     assert _lib.SIGNATURES["ncn_batch_labels_fw"] == [P, P, I64, P, P, P, I32, I64, P, P, P, P]
-    fwd = _lib.GEOM_ABI["ncn_geom_loss_fwd"][1]
+    fwd = _lib.ABI["ncn_geom_loss_fwd"][1]
     assert fwd[16] == ("ptr", 8, "ws") and fwd[19] == ("ptr", 8, "counts") and fwd[13] == ("ptr", 8, "step_dev")
 
 
@@ -62,7 +51,7 @@ def test_library_binds_the_new_names_as_int():
 
 def test_header_constants_match_the_package():
     from ncnerf_amd import losses
-    text = open(_lib.GEOM_HEADER_PATH).read()
+    text = _lib.read_header(HEADER)
     got = {k: int(v) for k, v in re.findall(r"^#define NCN_GEOM_(\w+) (\d+)$", text, flags=re.M)}
     assert got == {"DEPTH": losses.GEOM_DEPTH, "NORM_L1": losses.GEOM_NORM_L1, "NORM_DOT": losses.GEOM_NORM_DOT,
                    "REG": losses.GEOM_REG} == {"DEPTH": 1, "NORM_L1": 2, "NORM_DOT": 4, "REG": 8}
@@ -72,19 +61,16 @@ def test_header_constants_match_the_package():
         6, 6, 6, 12, 192, 6144, 6144, 6144]
 
 
-def test_a_name_in_two_headers_is_an_error(monkeypatch, tmp_path):
-    clash = tmp_path / "ncnerf_geom.h"
-    clash.write_text("int ncn_geom_loss_fwd(int a, void* stream);\nint ncn_version(void);\n")
-    monkeypatch.setattr(_lib, "GEOM_HEADER_PATH", str(clash))
-    with pytest.raises(_lib.NcnError, match="ncn_version is declared in include/ncnerf_geom.h and in"):
-        _lib._parse_geom_header(_lib.ABI)
+def test_a_name_in_two_headers_is_an_error(tmp_path):
+    clash = altered_headers(tmp_path, HEADER, "int ncn_geom_loss_fwd(int a, void* stream);\nint ncn_version(void);\n")
+    with pytest.raises(_lib.NcnError, match="ncn_version is declared in include/ncnerf_geom.h and in include/ncnerf.h"):
+        _lib.load_headers(clash)
 
 
-def test_missing_geom_header_names_the_path(monkeypatch, tmp_path):
-    path = str(tmp_path / "include" / "ncnerf_geom.h")
-    monkeypatch.setattr(_lib, "GEOM_HEADER_PATH", path)
-    with pytest.raises(_lib.NcnError, match=re.escape(path)):
-        _lib._read_geom_header()
+def test_missing_geom_header_names_the_path(tmp_path):
+    gone = altered_headers(tmp_path, HEADER)
+    with pytest.raises(_lib.NcnError, match=re.escape(os.path.join(gone, HEADER)) + ".*geometry supervision"):
+        _lib.load_headers(gone)
 
 
 # ---- refusals precede the call ----

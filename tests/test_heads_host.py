@@ -2,6 +2,7 @@
 precede the library, the model's parameters and flat buffers, the loss constructor.  No GPU."""
 import ctypes
 import os
+import re
 
 import pytest
 import torch
@@ -10,32 +11,29 @@ from ncnerf_amd import _lib, ngp_mt
 from ncnerf_amd.losses import NeRFMTLoss
 from ncnerf_amd.ngp_mt import NGPMT
 from ncnerf_amd.trainer import HYPERSIM_HPARAMS
+from test_abi import NAMES as ALL_NAMES, altered_headers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {"ncn_head_packed_halves", "ncn_head_pack_weights", "ncn_head_fwd", "ncn_head_feat", "ncn_head_bwd_blocks", "ncn_head_bwd",
-         "ncn_head_reduce_wgrad", "ncn_composite_extra_fw", "ncn_composite_extra_bw"}
+HEADER = "ncnerf_heads.h"
+NAMES = ALL_NAMES[HEADER]
 
 
 def test_header_parses_into_its_own_table():
-    text = open(os.path.join(ROOT, "include", "ncnerf_heads.h")).read()
-    fifth = _lib.parse_header(text)
-    assert set(fifth) == NAMES and _lib.HEADS_ABI == fifth and set(_lib.heads_symbols()) == NAMES
-    assert all(ret == "int" for ret, _ in fifth.values())
-    for table in _lib.ALL_TABLES:  # no name of another header
-        assert not set(table) & NAMES
-    assert _lib.BOUND_TABLES == _lib.ALL_TABLES + (_lib.HEADS_ABI,)
-    assert fifth["ncn_head_fwd"][1][0] == ("ptr", 2, "enc_cache") and fifth["ncn_head_fwd"][1][-1] == ("ptr", 0, "stream")
+    """(what every header shares, its names among it, is in test_abi.py)"""
+    assert _lib.header_path(HEADER) == os.path.join(ROOT, "include", HEADER)
+    assert set(_lib.symbols(HEADER)) == NAMES
+    fwd = _lib.ABI["ncn_head_fwd"][1]
+    assert fwd[0] == ("ptr", 2, "enc_cache") and fwd[-1] == ("ptr", 0, "stream")
 
 
-def test_name_clash_with_another_header_is_an_error(monkeypatch, tmp_path):
-    clash = tmp_path / "ncnerf_heads.h"
-    clash.write_text("int ncn_morton3D(const int32_t* coords, int64_t n, int32_t* out, void* stream);\n")
-    monkeypatch.setattr(_lib, "HEADS_HEADER_PATH", str(clash))
-    with pytest.raises(_lib.NcnError, match="ncn_morton3D.*ncnerf_heads.h"):
-        _lib._parse_heads_header(_lib.ALL_TABLES)
-    monkeypatch.setattr(_lib, "HEADS_HEADER_PATH", str(tmp_path / "missing.h"))
-    with pytest.raises(_lib.NcnError, match="missing.h"):
-        _lib._read_heads_header()
+def test_name_clash_with_another_header_is_an_error(tmp_path):
+    clash = altered_headers(tmp_path, HEADER,
+                            "int ncn_morton3D(const int32_t* coords, int64_t n, int32_t* out, void* stream);\n")
+    with pytest.raises(_lib.NcnError, match="ncn_morton3D is declared in include/ncnerf_heads.h and in include/ncnerf.h"):
+        _lib.load_headers(clash)
+    gone = altered_headers(tmp_path, HEADER)
+    with pytest.raises(_lib.NcnError, match=re.escape(os.path.join(gone, HEADER)) + ".*semantic / normal heads"):
+        _lib.load_headers(gone)
 
 
 def test_every_name_binds_with_int_restype():

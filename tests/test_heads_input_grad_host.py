@@ -9,17 +9,19 @@ import pytest
 import torch
 
 from ncnerf_amd import _lib
+from test_abi import altered_headers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = "ncnerf_input_grad.h"
 NAME = "ncn_field_bwd_mlp_rgb_din"
 P, I64, I32 = _lib.P, _lib.I64, _lib.I32
 
 
 def test_header_declares_the_entry_point_in_the_grammar():
-    path = os.path.join(ROOT, "include", "ncnerf_input_grad.h")
-    assert _lib.INPUT_GRAD_HEADER_PATH == path
-    seventh = _lib.parse_header(open(path).read())
-    assert set(seventh) == {NAME} and _lib.INPUT_GRAD_ABI == seventh and _lib.input_grad_symbols() == [NAME]
+    """(what every header shares, its names among it, is in test_abi.py)"""
+    assert _lib.header_path(HEADER) == os.path.join(ROOT, "include", HEADER)
+    seventh = _lib.parse_header(_lib.read_header(HEADER))
+    assert set(seventh) == {NAME} and _lib.symbols(HEADER) == [NAME]
     ret, params = seventh[NAME]
     assert ret == "int" and params[-1] == ("ptr", 0, "stream")
     assert [p[2] for p in params] == ["xyzs", "dirs", "n", "n_dev", "order", "weights_packed", "precision", "enc_cache",
@@ -27,13 +29,7 @@ def test_header_declares_the_entry_point_in_the_grammar():
                                       "w_master", "dL_ddirs", "stream"]
     assert params[1] == ("ptr", 4, "dirs") and params[5] == ("ptr", 2, "weights_packed") and params[16] == ("ptr", 4, "dL_ddirs")
     assert _lib.SIGNATURES[NAME] == [P, P, I64, P, P, P, I32, P, P, P, I32, P, P, P, P, P, P, P]
-    for table in _lib.LOADED_TABLES:  # no name of another header
-        assert NAME not in table
-    assert _lib.EVERY_TABLE == _lib.LOADED_TABLES + (_lib.INPUT_GRAD_ABI,)
     assert _lib.declaration(NAME) == seventh[NAME]
-    # independent of the parser: the one `ncn_name(` of the header outside its comments
-    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    assert set(re.findall(r"\b(ncn_\w+)\s*\(", text)) == {NAME}
     # the arguments are part 1's of ncn_field_bwd_mlp_part (without the sigma terms and `part`), then
     # ncn_field_bwd_mlp_din's two last
     part = [p for p in _lib.declaration("ncn_field_bwd_mlp_part")[1] if p[2] not in ("dL_dsigmas", "dL_dsigmas2", "part")]
@@ -48,15 +44,14 @@ def test_library_exports_the_entry_point():
     assert fn.restype is ctypes.c_int and list(fn.argtypes) == _lib.SIGNATURES[NAME]
 
 
-def test_name_clash_and_missing_header(monkeypatch, tmp_path):
-    clash = tmp_path / "ncnerf_input_grad.h"
-    clash.write_text("int ncn_field_bwd_mlp_din(const float* xyzs, void* stream);\n")
-    monkeypatch.setattr(_lib, "INPUT_GRAD_HEADER_PATH", str(clash))
-    with pytest.raises(_lib.NcnError, match="ncn_field_bwd_mlp_din.*ncnerf_input_grad.h"):
-        _lib._parse_input_grad_header(_lib.LOADED_TABLES)
-    monkeypatch.setattr(_lib, "INPUT_GRAD_HEADER_PATH", str(tmp_path / "missing.h"))
-    with pytest.raises(_lib.NcnError, match="missing.h"):
-        _lib._read_input_grad_header()
+def test_name_clash_and_missing_header(tmp_path):
+    clash = altered_headers(tmp_path, HEADER, "int ncn_field_bwd_mlp_din(const float* xyzs, void* stream);\n")
+    with pytest.raises(_lib.NcnError, match="ncn_field_bwd_mlp_din is declared in include/ncnerf_input_grad.h and in "
+                                            "include/ncnerf.h"):
+        _lib.load_headers(clash)
+    gone = altered_headers(tmp_path, HEADER)
+    with pytest.raises(_lib.NcnError, match=re.escape(os.path.join(gone, HEADER)) + ".*direction gradient"):
+        _lib.load_headers(gone)
 
 
 def _args(**over):

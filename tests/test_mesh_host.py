@@ -15,26 +15,19 @@ import torch
 import mesh_ref
 from ncnerf_amd import _lib, mesh
 from ncnerf_amd._lib import F32, I32, I64, P
+from test_abi import NAMES as ALL_NAMES, altered_headers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {"ncn_mesh_points", "ncn_mesh_count", "ncn_mesh_scan", "ncn_mesh_emit_verts", "ncn_mesh_emit_faces"}
+HEADER = "ncnerf_mesh.h"
+NAMES = ALL_NAMES[HEADER]
 BOX = ((-0.5, -0.5, -0.5), (0.5, 0.5, 0.5))
 
 
 # ---- the ABI ----
 def test_mesh_header_parses_into_a_table_of_its_own():
-    assert _lib.MESH_HEADER_PATH == os.path.join(ROOT, "include", "ncnerf_mesh.h")
-    fourth = _lib.parse_header(open(_lib.MESH_HEADER_PATH).read())
-    assert set(fourth) == NAMES and _lib.MESH_ABI == fourth and set(_lib.mesh_symbols()) == NAMES
-    assert all(ret == "int" for ret, _ in fourth.values())
-    assert all(params[-1] == ("ptr", 0, "stream") for _, params in fourth.values())
-    # the other tables do not change: the training / validation surface is what it was
-    assert _lib.TABLES == (_lib.ABI, _lib.GEOM_ABI) and _lib.ALL_TABLES == _lib.TABLES + (_lib.MESH_ABI,)
-    assert not any(set(t) & NAMES for t in _lib.TABLES) and not set(_lib.exported_symbols()) & NAMES
-    for name in NAMES:
-        assert _lib.declaration(name) == fourth[name] and len(_lib.SIGNATURES[name]) == len(fourth[name][1])
-    text = re.sub(r"/\*.*?\*/", "", open(_lib.MESH_HEADER_PATH).read(), flags=re.S)
-    assert set(re.findall(r"\b(ncn_\w+)\s*\(", text)) == NAMES
+    """(what every header shares, its names among it, is in test_abi.py)"""
+    assert _lib.header_path(HEADER) == os.path.join(ROOT, "include", HEADER)
+    assert set(_lib.symbols(HEADER)) == NAMES <= set(_lib.exported_symbols())
 
 
 def test_known_signatures():
@@ -44,7 +37,7 @@ def test_known_signatures():
     assert _lib.SIGNATURES["ncn_mesh_scan"] == [P, I64, I32, P, P, P, P]
     assert _lib.SIGNATURES["ncn_mesh_emit_verts"] == [P, I64, I64, I64] + box + [F32, P, P, P, P, I64, P]
     assert _lib.SIGNATURES["ncn_mesh_emit_faces"] == [P, I64, I64, I64, F32, P, P, P, P, P, P, P, I64, P]
-    scan = _lib.MESH_ABI["ncn_mesh_scan"][1]
+    scan = _lib.ABI["ncn_mesh_scan"][1]
     assert scan[0] == ("ptr", 1, "in") and scan[3] == ("ptr", 2, "local") and scan[4] == ("ptr", 8, "block_base")
 
 
@@ -58,7 +51,7 @@ def test_library_binds_the_new_names_as_int():
 
 
 def test_header_constants_match_the_package():
-    text = open(_lib.MESH_HEADER_PATH).read()
+    text = _lib.read_header(HEADER)
     got = {k: int(v) for k, v in re.findall(r"^#define NCN_MESH_(\w+) (\d+)$", text, flags=re.M)}
     assert got == {"TILE_X": mesh.TILE[0], "TILE_Y": mesh.TILE[1], "TILE_Z": mesh.TILE[2],
                    "SCAN_ELEMS": mesh.SCAN_ELEMS, "SCAN_SWEEP": mesh.SCAN_SWEEP}
@@ -66,24 +59,22 @@ def test_header_constants_match_the_package():
     assert [mesh.blocks(n) for n in (1, mesh.SCAN_ELEMS, mesh.SCAN_ELEMS + 1)] == [1, 1, 2]
 
 
-def test_a_name_in_two_headers_is_an_error(monkeypatch, tmp_path):
-    clash = tmp_path / "ncnerf_mesh.h"
-    clash.write_text("int ncn_mesh_count(int a, void* stream);\nint ncn_geom_loss_fwd(int a, void* stream);\n")
-    monkeypatch.setattr(_lib, "MESH_HEADER_PATH", str(clash))
-    with pytest.raises(_lib.NcnError, match="ncn_geom_loss_fwd is declared in include/ncnerf_mesh.h and in another"):
-        _lib._parse_mesh_header(_lib.TABLES)
-    twice = tmp_path / "twice.h"
-    twice.write_text("int ncn_mesh_count(int a, void* stream);\nint ncn_mesh_count(int b, void* stream);\n")
-    monkeypatch.setattr(_lib, "MESH_HEADER_PATH", str(twice))
+def test_a_name_in_two_headers_is_an_error(tmp_path):
+    clash = altered_headers(tmp_path, HEADER, "int ncn_mesh_count(int a, void* stream);\n"
+                                              "int ncn_geom_loss_fwd(int a, void* stream);\n")
+    with pytest.raises(_lib.NcnError, match="ncn_geom_loss_fwd is declared in include/ncnerf_mesh.h and in "
+                                            "include/ncnerf_geom.h"):
+        _lib.load_headers(clash)
+    twice = altered_headers(tmp_path, HEADER, "int ncn_mesh_count(int a, void* stream);\n"
+                                              "int ncn_mesh_count(int b, void* stream);\n")
     with pytest.raises(ValueError, match="ncn_mesh_count is declared twice"):
-        _lib._parse_mesh_header(_lib.TABLES)
+        _lib.load_headers(twice)
 
 
-def test_missing_mesh_header_names_the_path(monkeypatch, tmp_path):
-    path = str(tmp_path / "include" / "ncnerf_mesh.h")
-    monkeypatch.setattr(_lib, "MESH_HEADER_PATH", path)
-    with pytest.raises(_lib.NcnError, match=re.escape(path)):
-        _lib._read_mesh_header()
+def test_missing_mesh_header_names_the_path(tmp_path):
+    gone = altered_headers(tmp_path, HEADER)
+    with pytest.raises(_lib.NcnError, match=re.escape(os.path.join(gone, HEADER)) + ".*isosurface extraction"):
+        _lib.load_headers(gone)
 
 
 # ---- refusals precede the call ----

@@ -10,8 +10,11 @@ import torch
 
 import metrics_ref as M
 from ncnerf_amd import _lib
+from test_abi import NAMES as ALL_NAMES, altered_headers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = "ncnerf_metrics.h"
+NAMES = ALL_NAMES[HEADER]
 BOUND0 = 2.0 ** -20
 
 
@@ -157,20 +160,9 @@ def test_compute_counts_only_the_views_that_counted():
 
 # ---------------------------------------------------------------- the second header
 def test_metrics_header_parses_into_the_one_table():
-    first = _lib.parse_header(open(_lib.HEADER_PATH).read())
-    second = _lib.parse_header(open(_lib.METRICS_HEADER_PATH).read())
-    assert _lib.METRICS_HEADER_PATH == os.path.join(ROOT, "include", "ncnerf_metrics.h")
-    assert set(second) == {"ncn_metrics_pointwise", "ncn_metrics_ssim", "ncn_metrics_angles", "ncn_select_median",
-                           "ncn_metrics_finalise"}
-    assert all(ret == "int" for ret, _ in second.values())
-    assert all(params[-1] == ("ptr", 0, "stream") for _, params in second.values())
-    assert not set(first) & set(second)
-    assert len(first) == 80 and set(_lib.ABI) == set(first) | set(second)
-    for name in second:
-        assert _lib.ABI[name] == second[name] and len(_lib.SIGNATURES[name]) == len(second[name][1])
-    # independent of the parser: every `ncn_name(` of the header
-    text = re.sub(r"/\*.*?\*/", "", open(_lib.METRICS_HEADER_PATH).read(), flags=re.S)
-    assert set(re.findall(r"\b(ncn_\w+)\s*\(", text)) == set(second)
+    """(what every header shares, its names among it, is in test_abi.py)"""
+    assert _lib.header_path(HEADER) == os.path.join(ROOT, "include", HEADER)
+    assert set(_lib.symbols(HEADER)) == NAMES
     P, I64, I32 = _lib.P, _lib.I64, _lib.I32
     assert _lib.SIGNATURES["ncn_select_median"] == [P, I64, I32, P, P, I64, P, P]
     assert _lib.ABI["ncn_metrics_ssim"][1][5] == ("ptr", 8, "ws")
@@ -178,7 +170,7 @@ def test_metrics_header_parses_into_the_one_table():
 
 def test_header_taps_are_torchs_float32_taps():
     """NCN_SSIM_TAPS, bit for bit the restatement's taps (the window's weight sum depends on them)."""
-    text = open(_lib.METRICS_HEADER_PATH).read()
+    text = _lib.read_header(HEADER)
     body = re.search(r"^#define NCN_SSIM_TAPS \{([^}]*)\}$", text, flags=re.M).group(1)
     taps = np.array([float.fromhex(t.strip().rstrip("f")) for t in body.split(",")])
     g = M.gaussian_taps32().numpy()
@@ -189,16 +181,15 @@ def test_header_taps_are_torchs_float32_taps():
 
 def test_library_exports_the_metric_entry_points():
     L = _lib.lib()
-    for name in _lib.parse_header(open(_lib.METRICS_HEADER_PATH).read()):
+    for name in NAMES:
         fn = getattr(L, name)
         assert fn.restype is _lib.I32 and list(fn.argtypes) == _lib.SIGNATURES[name]
 
 
-def test_missing_metrics_header_names_the_path(monkeypatch, tmp_path):
-    gone = str(tmp_path / "include" / "ncnerf_metrics.h")
-    monkeypatch.setattr(_lib, "METRICS_HEADER_PATH", gone)
-    with pytest.raises(_lib.NcnError, match=re.escape(gone)):
-        _lib._parse_headers()
+def test_missing_metrics_header_names_the_path(tmp_path):
+    gone = altered_headers(tmp_path, HEADER)
+    with pytest.raises(_lib.NcnError, match=re.escape(os.path.join(gone, HEADER)) + ".*validation metrics"):
+        _lib.load_headers(gone)
 
 
 def test_metric_calls_are_marshalled_like_the_others():

@@ -10,9 +10,11 @@ import torch
 import sem_metrics_ref as S
 from ncnerf_amd import _lib
 from ncnerf_amd import metrics as NM
+from test_abi import NAMES as ALL_NAMES, altered_headers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {"ncn_sem_confusion", "ncn_sem_finalise", "ncn_batch_semantics_fw"}
+HEADER = "ncnerf_sem.h"
+NAMES = ALL_NAMES[HEADER]
 NAN, INF = float("nan"), float("inf")
 ARGMAX_ROWS = [([1, 3, 3, 2], 1), ([NAN, 5, NAN, 1], 0), ([-INF] * 4, 0), ([2, NAN, 9, NAN], 1), ([INF, INF, 0, NAN], 3)]
 
@@ -51,17 +53,10 @@ def test_update_is_the_confusion_matrix():
 
 # ---------------------------------------------------------------- the sixth header
 def test_sem_header_parses_into_its_own_table():
-    path = os.path.join(ROOT, "include", "ncnerf_sem.h")
-    assert _lib.SEM_HEADER_PATH == path
-    sixth = _lib.parse_header(open(path).read())
-    assert set(sixth) == NAMES and _lib.SEM_ABI == sixth and set(_lib.sem_symbols()) == NAMES
-    assert all(ret == "int" for ret, _ in sixth.values())
-    assert all(params[-1] == ("ptr", 0, "stream") for _, params in sixth.values())
-    for table in _lib.BOUND_TABLES:  # no name of another header
-        assert not set(table) & NAMES
-    assert _lib.LOADED_TABLES == _lib.BOUND_TABLES + (_lib.SEM_ABI,)
-    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    assert set(re.findall(r"\b(ncn_\w+)\s*\(", text)) == NAMES
+    """(what every header shares, its names among it, is in test_abi.py)"""
+    assert _lib.header_path(HEADER) == os.path.join(ROOT, "include", HEADER)
+    sixth = _lib.parse_header(_lib.read_header(HEADER))
+    assert set(_lib.symbols(HEADER)) == NAMES == set(sixth)
     P, I64, I32 = _lib.P, _lib.I64, _lib.I32
     assert _lib.SIGNATURES["ncn_sem_confusion"] == [P, I64, P, I32, I32, I64, I32, P, P, P, P]
     assert _lib.SIGNATURES["ncn_sem_finalise"] == [P, I32, P, P]
@@ -80,15 +75,14 @@ def test_library_exports_the_semantic_entry_points():
         assert fn.restype is _lib.I32 and list(fn.argtypes) == _lib.SIGNATURES[name]
 
 
-def test_name_clash_and_missing_header(monkeypatch, tmp_path):
-    clash = tmp_path / "ncnerf_sem.h"
-    clash.write_text("int ncn_select_median(const float* vals, void* stream);\n")
-    monkeypatch.setattr(_lib, "SEM_HEADER_PATH", str(clash))
-    with pytest.raises(_lib.NcnError, match="ncn_select_median.*ncnerf_sem.h"):
-        _lib._parse_sem_header(_lib.BOUND_TABLES)
-    monkeypatch.setattr(_lib, "SEM_HEADER_PATH", str(tmp_path / "missing.h"))
-    with pytest.raises(_lib.NcnError, match="missing.h"):
-        _lib._read_sem_header()
+def test_name_clash_and_missing_header(tmp_path):
+    clash = altered_headers(tmp_path, HEADER, "int ncn_select_median(const float* vals, void* stream);\n")
+    with pytest.raises(_lib.NcnError, match="ncn_select_median is declared in include/ncnerf_sem.h and in "
+                                            "include/ncnerf_metrics.h"):
+        _lib.load_headers(clash)
+    gone = altered_headers(tmp_path, HEADER)
+    with pytest.raises(_lib.NcnError, match=re.escape(os.path.join(gone, HEADER)) + ".*semantic metrics"):
+        _lib.load_headers(gone)
 
 
 def test_refusals_precede_the_library(monkeypatch):
