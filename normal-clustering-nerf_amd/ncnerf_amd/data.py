@@ -10,9 +10,12 @@ targets of NeRFMTLoss's depth and GT-normal terms) gathers them for the drawn ra
 ncn_batch_labels_fw, and its batches carry them under those keys; a `semantics` plane of integer
 class labels (the target of NeRFMTLoss's semantic term and of the semantic metrics; 0 = void) is
 gathered behind it by ncn_batch_semantics_fw into int64 labels.  The batch is the dict
-Trainer.step(batch, ...) takes; the Trainer itself does not draw from a dataset yet.
+Trainer.step(batch, ...) takes, and Trainer.step_from(dataset, step) / Trainer.fit(dataset, n_steps)
+draw it themselves: the captured step begins with batch(device step counter, out=its static
+buffers, seed=seed + rank), so the launches above are nodes of its graph (trainer.py).
 With optimize_ext the dataset holds the reference's per-image pose corrections dR (axis-angle) and dT
-(train_nerf.py:244-249) and the rays carry their gradient (ncn_batch_rays_bw, deterministic).
+(train_nerf.py:244-249) and the rays carry their gradient (ncn_batch_rays_bw, deterministic); the
+eager step_from steps them (optim.PoseAdam).
 
 Only the two patch strategies are implemented (`all_images_triang_patch`, `same_image_triang_patch`).
 The draws are counter-based (seed, step, patch), not numpy's global generator.

@@ -41,6 +41,11 @@ def world_size():
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
 
+def rank():
+    """This process's rank (0 without a process group): the offset of its batch-draw seed."""
+    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+
+
 def is_distributed():
     return dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
 

@@ -16,6 +16,57 @@ from . import _lib
 from ._lib import call
 
 
+def cosine_factor(epoch, num_epochs):
+    """CosineAnnealingLR(T_max=num_epochs, eta_min=0) after `epoch` scheduler steps, as a factor of
+    the base learning rate (train_nerf.py:286-288): (1 + cos(pi * epoch / num_epochs)) / 2.  The
+    scheduler holds every parameter group of the optimizer, the pose group included."""
+    return 0.5 * (1 + math.cos(math.pi * epoch / num_epochs))
+
+
+POSE_LR = 1e-6  # train_nerf.py:275-277 ("learning rate is hard-coded")
+
+
+class PoseAdam:
+    """The reference's third parameter group, [dR, dT] (train_nerf.py:275-277): Adam at lr 1e-6, weight
+    decay 0, default betas, and the optimizer's default eps 1e-8 (the group sets none), on a few
+    (V, 3) tensors with torch ops: an eager group beside the captured field step.  A step whose
+    gradients are not all finite (the fp16 overflow step that ncn_adam_step skips for the field)
+    leaves parameters, moments and step count as they are; the test is a device select, not a host
+    read.  The gradients are not clipped."""
+
+    def __init__(self, params, lr=POSE_LR, betas=(0.9, 0.999), eps=1e-8):
+        self.params = list(params)
+        self.lr, self.betas, self.eps = lr, betas, eps
+        self.m = [torch.zeros_like(p) for p in self.params]
+        self.v = [torch.zeros_like(p) for p in self.params]
+        # applied steps, on the device: a skipped step does not count (fp64: 1 - beta^t without loss)
+        self.t = torch.zeros((), dtype=torch.float64, device=self.params[0].device)
+
+    def zero_grad(self):
+        for p in self.params:
+            p.grad = None
+
+    def state_tensors(self):
+        return self.params + self.m + self.v + [self.t]
+
+    @torch.no_grad()
+    def step(self, lr_factor=1.0):
+        """One Adam step at lr * lr_factor from the parameters' .grad (a missing one: zeros)."""
+        grads = [torch.zeros_like(p) if p.grad is None else p.grad for p in self.params]
+        ok = torch.stack([torch.isfinite(g).all() for g in grads]).all()
+        b1, b2 = self.betas
+        t = self.t + 1
+        c1, c2 = (1 - b1 ** t).float(), (1 - b2 ** t).float()
+        for p, g, m, v in zip(self.params, grads, self.m, self.v):
+            m_new = b1 * m + (1 - b1) * g
+            v_new = b2 * v + (1 - b2) * g * g
+            p_new = p - (self.lr * lr_factor) * (m_new / c1) / ((v_new / c2).sqrt() + self.eps)
+            p.copy_(torch.where(ok, p_new, p))
+            m.copy_(torch.where(ok, m_new, m))
+            v.copy_(torch.where(ok, v_new, v))
+        self.t.copy_(torch.where(ok, t, self.t))
+
+
 class FlatAdam:
     def __init__(self, model, lr=1e-2, betas=(0.9, 0.999), eps=1e-15, weight_decay=(0.0, 1e-6), max_norm=0.05,
                  num_epochs=None, zero_grad_on_step=False):
@@ -55,7 +106,7 @@ class FlatAdam:
         (also inside a captured graph); a no-op when the epoch is unchanged."""
         if self.num_epochs and epoch != self.epoch:
             self.epoch = epoch
-            self.lr = 0.5 * self.base_lr * (1 + math.cos(math.pi * epoch / self.num_epochs))
+            self.lr = self.base_lr * cosine_factor(epoch, self.num_epochs)  # (x 0.5 is exact: the value as before)
             self.lr_dev.fill_(self.lr)
 
     def step(self, grad_scale=1.0, gated=False):

@@ -6,7 +6,14 @@ learning rate (CosineAnnealingLR(T_max=num_epochs), train_nerf.py:286-288; an ep
 training set's 1000 items, base.py:78-81, split over the ranks by DDP's DistributedSampler).
 
 Hyper-parameters default to the Hypersim config (experiments/hypersim/hyperparameters.py);
-preset="scannet_manhattan" selects config #5's (experiments/scannet_man/hyperparameters.py)."""
+preset="scannet_manhattan" selects config #5's (experiments/scannet_man/hyperparameters.py).
+
+The training loop (the reference's trainer.fit(system)): Trainer.step_from(dataset, global_step) is
+the step with its batch drawn from a data.DeviceRayDataset — in the captured step the draw, the
+rays and the gathers are nodes of the graph that read the device step counter, so a replay copies
+no batch — and Trainer.fit(dataset, n_steps) runs it over a step range, steps the dataset's pose
+corrections dR / dT (eager step, optimize_ext), and keeps the per-step log (losses, sample counts)
+in a device ring that is read once per drain (TrainLog)."""
 import math
 import warnings
 
@@ -14,7 +21,7 @@ import torch
 
 from . import _lib, distributed
 from .losses import NeRFMTLoss, check_cluster_status
-from .optim import FlatAdam
+from .optim import POSE_LR, FlatAdam, PoseAdam, cosine_factor
 from .rendering import march_train_fused, render
 
 HYPERSIM_HPARAMS = dict(
@@ -39,6 +46,83 @@ def hparams_for(preset):
     if preset not in PRESETS:
         raise ValueError(f"unknown preset {preset!r}; one of {sorted(PRESETS)}")
     return dict(PRESETS[preset])
+
+
+_HOST_BATCH = "batch"  # Trainer._source of a graph captured from step()'s host-built dict
+
+
+def rank_seed(dataset):
+    """The seed this rank draws its batches with: the dataset's plus the rank (every rank of a
+    data-parallel run draws its own 8192 rays, base.py:94-171 under DDP's per-rank workers)."""
+    return dataset.seed + distributed.rank()
+
+
+def pose_lr(epoch, num_epochs):
+    """The learning rate of the pose group [dR, dT] in `epoch`: the hard-coded 1e-6 (train_nerf.py:
+    275-277) under the scheduler's per-epoch cosine factor (:286-288), which holds every group."""
+    return POSE_LR * (cosine_factor(epoch, num_epochs) if num_epochs else 1.0)
+
+
+class TrainLog:
+    """The per-step log of Trainer.fit, decoded on the host.  Rows come from the device ring
+    (`add_ring`): float32 columns `step`, `total`, the loss terms in the order of the step's loss
+    dict, `rm_samples`, `vr_samples` (exact in float32 below 2^24).  log[name] is the column as a
+    float32 tensor in step order (NaN where a step had no such term); derived columns, as the
+    reference logs them: `psnr` = -10 log10(rgb) (train/psnr: PSNR at data range 1 of the step's
+    batch, train_nerf.py:348,353), `rm_s` / `vr_s` = marched / composited samples per ray
+    (train_nerf.py:350-352).  log.steps: the step column as int64."""
+
+    HEAD, TAIL = ("step", "total"), ("rm_samples", "vr_samples")
+
+    def __init__(self, n_rays):
+        self.n_rays = int(n_rays)
+        self._segments = []  # (column names, (n, n_cols) float32 CPU rows)
+
+    @classmethod
+    def column_names(cls, loss_d):
+        """The ring's columns for a step whose loss dict is `loss_d` (`total` moved to the front)."""
+        return cls.HEAD + tuple(k for k in loss_d if k != "total") + cls.TAIL
+
+    @staticmethod
+    def ring_rows(first_step, count, capacity):
+        """Ring rows of the steps [first_step, first_step + count), in step order: step s is at s % capacity."""
+        if count > capacity:
+            raise ValueError(f"{count} steps do not fit a ring of {capacity} rows: drained too late")
+        return [(first_step + i) % capacity for i in range(count)]
+
+    def add_ring(self, ring, columns, first_step, count):
+        """Append the rows of `count` steps from `first_step` on out of a host copy of the ring."""
+        ring = torch.as_tensor(ring, dtype=torch.float32, device="cpu")
+        if ring.dim() != 2 or ring.shape[1] != len(columns):
+            raise ValueError(f"ring {tuple(ring.shape)} does not hold the {len(columns)} columns {tuple(columns)}")
+        if count > 0:
+            self._segments.append((tuple(columns), ring[self.ring_rows(first_step, count, ring.shape[0])].clone()))
+
+    def __len__(self):
+        return sum(rows.shape[0] for _, rows in self._segments)
+
+    @property
+    def columns(self):
+        """Every stored column name, in first-seen order."""
+        names = []
+        for cols, _ in self._segments:
+            names += [c for c in cols if c not in names]
+        return tuple(names)
+
+    def __getitem__(self, name):
+        if name == "psnr":
+            return -10.0 * torch.log10(self["rgb"])
+        if name in ("rm_s", "vr_s"):
+            return self[name[:2] + "_samples"] / float(self.n_rays)
+        if name not in self.columns:
+            raise KeyError(name)
+        parts = [rows[:, cols.index(name)] if name in cols else torch.full((rows.shape[0],), float("nan"))
+                 for cols, rows in self._segments]
+        return torch.cat(parts) if parts else torch.empty(0)
+
+    @property
+    def steps(self):
+        return self["step"].to(torch.int64) if self._segments else torch.empty(0, dtype=torch.int64)
 
 
 class Trainer:
@@ -95,6 +179,16 @@ class Trainer:
         self._rng_seed = int(torch.randint(0, 2 ** 62, (1,)).item())  # marcher jitter stream (CPU generator)
         # optional seed of each grid refresh (global_step -> int); default: drawn from torch's CPU generator
         self.grid_seed = None
+        self.last_batch = None  # the dict the last step trained on (graph step: the static buffers)
+        # what the captured graph takes its batch from: None (not captured), _HOST_BATCH (step(): copies
+        # of a host-built dict) or the DeviceRayDataset whose draw is captured (step_from())
+        self._source = None
+        self.pose_opt = None  # PoseAdam of the dataset's dR / dT (eager step_from, optimize_ext)
+        self._pose_ds = None
+        self._log_ring = self._log_buf = self._log_cols = self._log_step = None  # fit()'s device log
+        self._log_capacity = self.log_capacity
+
+    log_capacity = 1024  # rows of the log ring when a step_from() captures the graph before any fit()
 
     def flush_optimizer(self):
         """Apply the deferred optimizer step (defer_optimizer) now, if one is pending."""
@@ -117,10 +211,15 @@ class Trainer:
     # HIP graph: the marcher's sample count stays on the device (static_shapes), the loss-weight
     # schedule and Adam's step/lr are device scalars, so nothing in the step reads the host.  A
     # replay costs one launch instead of ~150 Python-driven ones.  Inputs are copied into the
-    # graph's static batch buffers; the occupancy-grid refresh and the RCCL all-reduce (N > 1)
-    # run eagerly around it.
+    # graph's static batch buffers (step()), or drawn into them by the graph's own first nodes
+    # (step_from(): DeviceRayDataset.batch on the device step counter, and the log row behind the
+    # body); the occupancy-grid refresh and the RCCL all-reduce (N > 1) run eagerly around it.
     def _body(self, batch, step_dev, with_opt):
         m = self.model
+        if self._source is not _HOST_BATCH:
+            # the draw, the rays and the gathers as nodes of the graph, reading the device step counter;
+            # on the main stream, ahead of the fork below (the marcher beside the optimizer reads the rays)
+            batch = self._source.batch(step_dev, out=batch, seed=self._seed)
         kw = dict(self.render_kwargs, global_step=0, static_shapes=True)
         kw["count_in_loss"] = True  # vr_samples summed by the loss node's first launch (no launch of its own)
         if "march_noise" in batch:
@@ -159,7 +258,28 @@ class Trainer:
             torch.autograd.backward(loss_d["total"], grad_tensors=self._unit(loss_d["total"].device))
         if with_opt and not self.defer:
             self.opt.step()
+        if self._source is not _HOST_BATCH:  # (the log row directly behind the body: captured with it)
+            self._log_row(results, loss_d, step_dev)
         return results, loss_d
+
+    def _log_row(self, results, loss_d, step_dev):
+        """One row of the device log: (step, total, the loss terms, rm_samples, vr_samples) as float32
+        into row step % capacity of the ring, by device ops that read the step's outputs and the
+        device step counter (capturable: no host value, nothing allocated after the first call)."""
+        cols = TrainLog.column_names(loss_d)
+        if self._log_ring is None or cols != self._log_cols:
+            f = dict(dtype=torch.float32, device=step_dev.device)
+            self._log_ring, self._log_buf, self._log_cols = torch.zeros(self._log_capacity, len(cols), **f), torch.zeros(
+                len(cols), **f), cols
+        with torch.no_grad():
+            row, n = self._log_buf, len(cols)
+            # the float terms in one launch; the three integers (int64, int32, int64) by a converting copy each
+            torch.stack([loss_d["total"]] + [loss_d[k] for k in cols[2:-2]], out=row[1:n - 2])
+            row[0].copy_(step_dev)
+            row[n - 2].copy_(results["rm_samples"])
+            row[n - 1].copy_(results["vr_samples"])
+            at = torch.remainder(step_dev, self._log_ring.shape[0]).reshape(1)
+            self._log_ring.index_copy_(0, at, row.reshape(1, n))
 
     def _unit(self, dev):
         """A device fp32 1.0: the upstream gradient of the total loss."""
@@ -172,12 +292,22 @@ class Trainer:
             self._side = torch.cuda.Stream(device=self.model.flat_params().device)
         return self._side
 
-    def _capture(self, batch):
-        import torch
-        dev = batch["rays_o"].device
+    def _capture(self, batch, dataset=None):
+        """Capture the step.  batch: a host-built dict, cloned into the static buffers that every
+        replay's inputs are copied into; or dataset: the static buffers are its buffers() plus the
+        constant entries, and the body begins with its draw."""
         if self.render_kwargs.get("anneal_steps", 0) > 0:
             raise NotImplementedError("ray-range annealing is step-dependent host control flow")
-        self._static = {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in batch.items()}
+        if dataset is not None:
+            dev = dataset.device
+            self._static = dict(dataset.buffers(), patch_area=dataset.patch_size * dataset.patch_size,
+                                x1_offsets_local=dataset.x1_off, x2_offsets_local=dataset.x2_off,
+                                x3_offsets_local=dataset.x3_off)
+            self._seed = rank_seed(dataset)
+        else:
+            dev = batch["rays_o"].device
+            self._static = {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in batch.items()}
+        self._source = _HOST_BATCH if dataset is None else dataset
         from .split_step import SplitStep, split_eligible
         self._split = None
         if self.split_backward and split_eligible(self, self._static):
@@ -227,11 +357,14 @@ class Trainer:
         self.opt.step_count = saved_count
         self.model.flat_grad().zero_()  # (the warm-ups without the optimizer left gradients behind)
 
-    def _graph_step(self, batch, global_step):
+    def _graph_step(self, batch, global_step, dataset=None):
+        """batch: the host-built dict to copy into the static buffers; or dataset (batch None): the
+        captured draw fills them, and the replay's only inputs are the step counter and the gate."""
         if self.graph is None:
-            self._capture(batch)
+            self._capture(batch, dataset)
+        self.last_batch = self._static
         dst, src = [], []
-        for k, v in batch.items():
+        for k, v in ({} if batch is None else batch).items():
             if k in self._static and hasattr(v, "copy_") and v is not self._static[k]:
                 dst.append(self._static[k])
                 src.append(v)
@@ -260,17 +393,38 @@ class Trainer:
 
     status_interval = 100  # steps between reads of the clustering kernel's error word
 
-    def step(self, batch, global_step):
-        m = self.model
+    def _check_source(self, dataset):
+        """One captured graph serves one source.  dataset: None for step()'s host-built batch.  Raises
+        before anything is launched."""
+        if not self.use_graph:
+            return
+        if dataset is not None and dataset.optimize_ext:
+            raise NotImplementedError(
+                "Trainer(use_graph=True) cannot refine the poses of a dataset with optimize_ext: the captured step "
+                "renders with static shapes, and that render refuses rays that require grad (rendering.render; "
+                "RayMarcher.backward has no static-capacity ray gradient).  Use Trainer(use_graph=False).")
+        want = _HOST_BATCH if dataset is None else dataset
+        if self._source is None or self._source is want:
+            return
+        have = ("a host-built batch (step())" if self._source is _HOST_BATCH
+                else "the DeviceRayDataset of its first step_from(): the draw is part of the graph")
+        raise RuntimeError(f"the captured step takes its batch from {have}; it cannot train on "
+                           f"{'a host-built batch' if dataset is None else 'another source'}.  "
+                           "Use one Trainer per source.")
+
+    def _prologue(self, global_step):
+        """What surrounds every step: the cluster status word, the grid refresh, the epoch's learning rate."""
         if global_step % self.status_interval == 0:
-            check_cluster_status(m.flat_params().device)  # (raises if an earlier launch timed out)
+            check_cluster_status(self.model.flat_params().device)  # (raises if an earlier launch timed out)
         self._maybe_update_grid(global_step)
         epoch = global_step // self.steps_per_epoch
         if epoch != self.opt.epoch:
             self.flush_optimizer()  # (a pending step belongs to the previous epoch's learning rate)
         self.opt.set_epoch(epoch)
-        if self.use_graph:
-            return self._graph_step(batch, global_step)
+
+    def _eager_step(self, batch, global_step):
+        m = self.model
+        self.last_batch = batch
         kw = dict(self.render_kwargs, global_step=global_step)
         if "march_noise" in batch:
             kw["march_noise"] = batch["march_noise"]
@@ -279,3 +433,88 @@ class Trainer:
         loss_d["total"].backward()
         self.opt.step(grad_scale=distributed.reduce_gradients(m))
         return results, loss_d
+
+    def step(self, batch, global_step):
+        self._check_source(None)
+        self._prologue(global_step)
+        if self.use_graph:
+            return self._graph_step(batch, global_step)
+        return self._eager_step(batch, global_step)
+
+    def step_from(self, dataset, global_step):
+        """step() with the batch of `global_step` drawn from `dataset` (a data.DeviceRayDataset) with
+        this rank's seed (rank_seed); same return value.  Graph step: the first call captures the draw
+        with the step (see _capture), a replay copies no batch; the graph then serves this dataset
+        only.  Eager step: with dataset.optimize_ext the pose corrections dR / dT take their Adam step
+        too (optim.PoseAdam at pose_lr of the epoch; their gradients are cleared before every step, and
+        a step with a non-finite pose gradient leaves them and their moments untouched)."""
+        self._check_source(dataset)
+        pose = None
+        if dataset.optimize_ext:
+            if self.world > 1:
+                raise NotImplementedError("pose refinement is single-process: the pose gradients are not all-reduced")
+            if self._pose_ds is not dataset:
+                self.pose_opt, self._pose_ds = PoseAdam([dataset.dR, dataset.dT]), dataset
+            pose = self.pose_opt
+        self._prologue(global_step)
+        if self.use_graph:
+            return self._graph_step(None, global_step, dataset)
+        if pose is not None:
+            pose.zero_grad()
+        out = self._eager_step(dataset.batch(global_step, seed=rank_seed(dataset)), global_step)
+        if pose is not None:
+            pose.step(cosine_factor(self.opt.epoch, self.h["num_epochs"]) if self.h.get("num_epochs") else 1.0)
+        return out
+
+    def fit(self, dataset, n_steps, start_step=0, callback=None, callback_every=0, log_capacity=None):
+        """Train on `dataset` for the steps [start_step, start_step + n_steps) (step_from each) and
+        return their TrainLog.
+
+        After every step one row (TrainLog's columns) goes into a device ring at row step % capacity,
+        written by device ops — in the graph step captured once, directly behind the body, so a replay
+        logs with no Python work.  log_capacity (default n_steps) is the ring's rows; the ring is read
+        back ("drained", one copy) every log_capacity steps and at the end, and between drains fit
+        reads nothing from the device but the cluster status word every `status_interval` steps.  The
+        ring belongs to the captured graph: a later fit on the same trainer keeps its rows and drains
+        at least that often.
+
+        callback(trainer, global_step), callback_every > 0: called after the step `global_step`
+        whenever (global_step + 1) % callback_every == 0, i.e. each time the total number of steps
+        trained reaches a multiple of callback_every; flush_optimizer() has run, so the model holds
+        the parameters after that step (a validation render, evaluation.evaluate_views, goes here).
+        At the end a pending deferred optimizer step is flushed."""
+        n_steps, start_step = int(n_steps), int(start_step)
+        capacity = n_steps if log_capacity is None else int(log_capacity)
+        if n_steps < 1 or capacity < 1:
+            raise ValueError(f"fit: n_steps {n_steps} and log_capacity {capacity} must be at least 1")
+        self._check_source(dataset)
+        if self.graph is None:  # (a captured graph keeps the ring it was captured with)
+            self._log_capacity = capacity
+            self._log_ring = None
+        log = TrainLog(dataset.batch_size)
+        first = start_step  # the first step whose row is still on the device only
+        for s in range(start_step, start_step + n_steps):
+            results, loss_d = self.step_from(dataset, s)
+            if not self.use_graph:
+                if self._log_step is None:
+                    self._log_step = torch.zeros((), dtype=torch.int64, device=dataset.device)
+                self._log_step.fill_(s)
+                cols = TrainLog.column_names(loss_d)
+                if self._log_ring is not None and cols != self._log_cols and s > first:
+                    self._drain(log, first, s - first)  # (a term switched on: the ring changes its columns)
+                    first = s
+                self._log_row(results, loss_d, self._log_step)
+            if s + 1 - first == min(capacity, self._log_ring.shape[0]):
+                self._drain(log, first, s + 1 - first)
+                first = s + 1
+            if callback is not None and callback_every > 0 and (s + 1) % callback_every == 0:
+                self.flush_optimizer()
+                callback(self, s)
+        self.flush_optimizer()
+        self._drain(log, first, start_step + n_steps - first)
+        return log
+
+    def _drain(self, log, first_step, count):
+        """The ring's rows of `count` steps into the host log: one device-to-host copy."""
+        if count > 0:
+            log.add_ring(self._log_ring.cpu(), self._log_cols, first_step, count)
