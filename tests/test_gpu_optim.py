@@ -6,13 +6,18 @@ relative + 1e-8; (b) torch.optim.AdamW, which forms (1 - beta) in double where a
 tolerance 2e-6 relative + 5e-7.  Both after clip_grad_norm_(max_norm) on the scaled gradient and
 with the reference's two groups (hash grid wd 0, nets wd 1e-6, eps 1e-15; train_nerf.py:262-285,
 955).
-Covers grad_scale != 1 (DDP's 1/world), an odd n (scalar tail), an odd group boundary, clipped and
-unclipped norms, n beyond one grid-stride of the Adam launch, and the zero_grad fold."""
+Covers grad_scale != 1 (DDP's 1/world), an odd n (scalar tail), clipped and unclipped norms, n
+beyond one grid-stride of the Adam launch, and the zero_grad fold; m and v of the same runs against
+the restatement's by the bounds of tests/optim_state.py.  Not covered here: with these settings the
+parameters show neither the gradient's scale nor a weight decay of 1e-6, so neither the group
+boundary nor the decay itself — tests/test_gpu_optim_state.py runs both with a decay of (0.5,
+0.25), and pins the clip factor, eps and the late steps' bias corrections."""
 import math
 
 import pytest
 import torch
 
+import optim_state
 from ncnerf_amd.optim import FlatAdam
 
 pytestmark = pytest.mark.gpu
@@ -29,21 +34,30 @@ class _Flat:
         return self._g
 
 
-def _apex_reference(p0, grads, n0, scale, lr, max_norm, wd=(0.0, 1e-6), b1=0.9, b2=0.999, eps=1e-15):
-    p, m, v = p0.clone(), torch.zeros_like(p0), torch.zeros_like(p0)
+def _apex_reference(p0, grads, n0, scale, lr, max_norm, wd=(0.0, 1e-6), b1=0.9, b2=0.999, eps=1e-15,
+                    start_step=0, m0=None, v0=None, return_state=False):
+    """The k-th gradient is step start_step + k (bias corrections 1 - beta ** (start_step + k), in
+    double), from the moments m0 / v0 (zeros).  max_norm <= 0: no clipping (the kernels' branch).
+    return_state: (p, m, v, s_m) with s_m = b1 s_m + (1 - b1) |g cf| in fp64 from |m0|, the running
+    sum of the magnitudes that m adds up with both signs: the scale of m's rounding error."""
+    p = p0.clone()
+    m = torch.zeros_like(p0) if m0 is None else m0.clone()
+    v = torch.zeros_like(p0) if v0 is None else v0.clone()
+    s_m = m.double().abs()
     wdv = torch.full_like(p0, wd[1])
     wdv[:n0] = wd[0]
     fb1, fb2 = torch.tensor(b1, dtype=torch.float32), torch.tensor(b2, dtype=torch.float32)
-    for st, g in enumerate(grads, 1):
+    for st, g in enumerate(grads, start_step + 1):
         gs = g * scale
         norm = float(gs.double().norm())
-        gi = gs * min(1.0, max_norm / (norm + 1e-6))
+        gi = gs * (min(1.0, max_norm / (norm + 1e-6)) if max_norm > 0 else 1.0)
         m = fb1 * m + (1 - fb1) * gi
         v = fb2 * v + (1 - fb2) * gi * gi
+        s_m = b1 * s_m + (1 - b1) * gi.double().abs()
         bc1, bc2 = 1 - b1 ** st, 1 - b2 ** st
         upd = (m / bc1) / (torch.sqrt(v / bc2) + eps) + wdv * p
         p = p - lr * upd
-    return p
+    return (p, m, v, s_m) if return_state else p
 
 
 def _torch_reference(p0, grads, n0, scale, lr, max_norm, wd=(0.0, 1e-6)):
@@ -76,12 +90,15 @@ def test_adam_step_matches_torch_adamw(dev, n, n0, scale, gmag, steps):
         opt.step(grad_scale=scale)
         assert int(m.flat_grad().count_nonzero()) == 0  # gradient consumed and zeroed
     got = m.flat_params()
-    for ref, atol in ((_apex_reference(p0, grads, n0, scale, 1e-2, 0.05), 1e-8),
+    apex = _apex_reference(p0, grads, n0, scale, 1e-2, 0.05, return_state=True)
+    for ref, atol in ((apex[0], 1e-8),
                       (_torch_reference(p0, grads, n0, scale, 1e-2, 0.05), 5e-7)):
         err = (got - ref).abs()
         bad = int((err > 2e-6 * ref.abs() + atol).sum())
         assert bad == 0, (atol, bad, float(err.max()))
     assert int(opt.step_dev.item()) == steps
+    # the moments too: the parameters do not show the gradient's scale (tests/optim_state.py)
+    optim_state.check_state(got, opt.m, opt.v, apex, n, f"adamw n {n} scale {scale} gmag {gmag}")
 
 
 def test_adam_step_keeps_grad_without_fold(dev):
