@@ -13,13 +13,18 @@ the step with its batch drawn from a data.DeviceRayDataset — in the captured s
 rays and the gathers are nodes of the graph that read the device step counter, so a replay copies
 no batch — and Trainer.fit(dataset, n_steps) runs it over a step range, steps the dataset's pose
 corrections dR / dT (eager step, optimize_ext), and keeps the per-step log (losses, sample counts)
-in a device ring that is read once per drain (TrainLog)."""
+in a device ring that is read once per drain (TrainLog).
+
+Checkpoints (the reference's ModelCheckpoint / --ckpt_path): Trainer.state_dict / load_state_dict
+snapshot and restore everything a step depends on, save_checkpoint / load_checkpoint put a file
+around them (checkpoint.py), and fit(checkpoint_every=, checkpoint_path=) saves inside the loop."""
 import math
+import os
 import warnings
 
 import torch
 
-from . import _lib, distributed
+from . import _lib, checkpoint, distributed
 from .losses import NeRFMTLoss, check_cluster_status
 from .optim import POSE_LR, FlatAdam, PoseAdam, cosine_factor
 from .rendering import march_train_fused, render
@@ -187,6 +192,7 @@ class Trainer:
         self._pose_ds = None
         self._log_ring = self._log_buf = self._log_cols = self._log_step = None  # fit()'s device log
         self._log_capacity = self.log_capacity
+        self._next_step = 0  # the last step passed to step() / step_from() plus one (a checkpoint's `next_step`)
 
     log_capacity = 1024  # rows of the log ring when a step_from() captures the graph before any fit()
 
@@ -437,9 +443,9 @@ class Trainer:
     def step(self, batch, global_step):
         self._check_source(None)
         self._prologue(global_step)
-        if self.use_graph:
-            return self._graph_step(batch, global_step)
-        return self._eager_step(batch, global_step)
+        out = self._graph_step(batch, global_step) if self.use_graph else self._eager_step(batch, global_step)
+        self._next_step = int(global_step) + 1
+        return out
 
     def step_from(self, dataset, global_step):
         """step() with the batch of `global_step` drawn from `dataset` (a data.DeviceRayDataset) with
@@ -453,20 +459,183 @@ class Trainer:
         if dataset.optimize_ext:
             if self.world > 1:
                 raise NotImplementedError("pose refinement is single-process: the pose gradients are not all-reduced")
-            if self._pose_ds is not dataset:
-                self.pose_opt, self._pose_ds = PoseAdam([dataset.dR, dataset.dT]), dataset
-            pose = self.pose_opt
+            pose = self._pose_adam(dataset)
         self._prologue(global_step)
         if self.use_graph:
-            return self._graph_step(None, global_step, dataset)
-        if pose is not None:
-            pose.zero_grad()
-        out = self._eager_step(dataset.batch(global_step, seed=rank_seed(dataset)), global_step)
-        if pose is not None:
-            pose.step(cosine_factor(self.opt.epoch, self.h["num_epochs"]) if self.h.get("num_epochs") else 1.0)
+            out = self._graph_step(None, global_step, dataset)
+        else:
+            if pose is not None:
+                pose.zero_grad()
+            out = self._eager_step(dataset.batch(global_step, seed=rank_seed(dataset)), global_step)
+            if pose is not None:
+                pose.step(cosine_factor(self.opt.epoch, self.h["num_epochs"]) if self.h.get("num_epochs") else 1.0)
+        self._next_step = int(global_step) + 1
         return out
 
-    def fit(self, dataset, n_steps, start_step=0, callback=None, callback_every=0, log_capacity=None):
+    def _pose_adam(self, dataset):
+        """The PoseAdam of `dataset`'s dR / dT (optimize_ext): made, with zero moments, the first time
+        the dataset is seen."""
+        if self._pose_ds is not dataset:
+            self.pose_opt, self._pose_ds = PoseAdam([dataset.dR, dataset.dT]), dataset
+        return self.pose_opt
+
+    # -- checkpoints -------------------------------------------------------------------------------
+    # What a resumed run needs (DESIGN.md §7 lists every buffer that survives a step as state or
+    # scratch): the flat parameters, the occupancy grid behind the bitfield, the GradScaler state, the
+    # optimizer's moments with its device step counter and learning rate and their host mirrors, the
+    # jitter seed, torch's CPU generator (grid-refresh seeds) and the device's (the eager marcher's
+    # jitter), the pose corrections with their Adam state, and the next step.  A load writes into the
+    # existing tensors: a captured graph names them by address.
+    def _state_tensors(self, dataset=None):
+        """{name: tensor} of every device tensor a checkpoint holds, under the names of its sections."""
+        m, opt = self.model, self.opt
+        t = {"model.flat": m.flat_params(), "model.density_bitfield": m.density_bitfield}
+        for k in ("density_grid", "amp_state"):
+            if getattr(m, k, None) is not None:
+                t["model." + k] = getattr(m, k)
+        t.update({"optimizer.m": opt.m, "optimizer.v": opt.v, "optimizer.step_dev": opt.step_dev,
+                  "optimizer.lr_dev": opt.lr_dev})
+        if dataset is not None and dataset.optimize_ext:
+            pose = self._pose_adam(dataset)
+            t.update({"pose.dR": dataset.dR, "pose.dT": dataset.dT, "pose.t": pose.t})
+            for i in range(len(pose.params)):
+                t[f"pose.m.{i}"], t[f"pose.v.{i}"] = pose.m[i], pose.v[i]
+        return t
+
+    def state_dict(self, dataset=None):
+        """A snapshot of the training state (fresh clones on the device; checkpoint.save moves them to
+        the CPU): see the section comment above.  A pending deferred optimizer step is applied first
+        (flush_optimizer), so it is never part of a checkpoint.  dataset: the DeviceRayDataset the run
+        draws from; its signature is recorded, and under optimize_ext its dR / dT and their PoseAdam
+        state are saved.  `hparams` is recorded only (a load warns where it differs).  The device log
+        is not state: a TrainLog covers one fit call."""
+        self.flush_optimizer()
+        dev = self.model.flat_params().device
+        state = {"format": checkpoint.FORMAT, "version": checkpoint.VERSION,
+                 "model_signature": checkpoint.model_signature(self.model), "hparams": dict(self.h),
+                 "model": {}, "optimizer": {"step_count": int(self.opt.step_count), "epoch": int(self.opt.epoch),
+                                            "lr": float(self.opt.lr)},
+                 "rng_seed": int(self._rng_seed), "torch_rng_state": torch.get_rng_state().clone(),
+                 "next_step": int(self._next_step)}
+        if dev.type == "cuda":
+            state["cuda_rng_state"] = torch.cuda.get_rng_state(dev).clone()
+        if dataset is not None:
+            state["dataset_signature"] = checkpoint.dataset_signature(dataset)
+        for name, t in self._state_tensors(dataset).items():
+            node, *path = name.split(".")
+            if node == "pose" and len(path) == 2:  # pose.m.i / pose.v.i: lists in parameter order
+                state.setdefault("pose", {}).setdefault(path[0], []).append(t.detach().clone())
+            else:
+                state.setdefault(node, {})[path[0]] = t.detach().clone()
+        return state
+
+    @staticmethod
+    def _state_lookup(state, name):
+        """The entry of `state` that _state_tensors calls `name`, or None."""
+        node = state
+        for k in name.split("."):
+            if isinstance(node, dict):
+                node = node.get(k)
+            elif isinstance(node, (list, tuple)) and k.isdigit() and int(k) < len(node):
+                node = node[int(k)]
+            else:
+                return None
+        return node
+
+    def load_state_dict(self, state, dataset=None):
+        """Continue from `state` (state_dict(), or checkpoint.load of a file).  Everything is checked
+        before anything changes — the format, the model's signature, with pose state in `state` the
+        dataset (needed then, with optimize_ext and the checkpoint's signature), every tensor's shape
+        and dtype — and a refusal (ValueError) leaves the trainer as it was.  Hyper-parameters that
+        differ from the recorded ones are listed in a warning, and so is a dataset whose signature
+        differs when no pose state depends on it; the trainer's own values stay.
+
+        The load copies into the existing tensors (no tensor is rebound, so a captured graph replays
+        on the loaded state), drops a pending deferred optimizer step, zeroes the flat gradient,
+        restores the optimizer's host mirrors, the jitter seed and both generators, and packs the MLP
+        fragments of the loaded weights (prepare_weights).  The captured step holds the jitter seed as
+        a constant: a trainer that has captured takes a checkpoint of the same seed only (its own
+        snapshots); load into a new Trainer otherwise.  Returns `next_step`."""
+        checkpoint.check_header(state, "the state")
+        m, opt = self.model, self.opt
+        checkpoint.check_signature(state.get("model_signature", {}), checkpoint.model_signature(m), "model")
+        has_pose = "pose" in state
+        if has_pose:
+            if dataset is None or not dataset.optimize_ext:
+                raise ValueError("the checkpoint holds pose corrections (dR / dT and their Adam state): load it with "
+                                 "the DeviceRayDataset(optimize_ext=True) they belong to")
+            checkpoint.check_signature(state.get("dataset_signature", {}), checkpoint.dataset_signature(dataset),
+                                       "dataset")
+        targets = self._state_tensors(dataset if has_pose else None)
+        problems, plan = [], []
+        for name, dst in targets.items():
+            src = self._state_lookup(state, name)
+            if not isinstance(src, torch.Tensor):
+                problems.append(f"{name}: missing")
+            elif tuple(src.shape) != tuple(dst.shape) or src.dtype != dst.dtype:
+                problems.append(f"{name}: {tuple(src.shape)} {src.dtype}, the trainer's is {tuple(dst.shape)} {dst.dtype}")
+            else:
+                plan.append((dst, src))
+        for k in ("density_grid", "amp_state"):
+            if isinstance(state.get("model", {}).get(k), torch.Tensor) and "model." + k not in targets:
+                problems.append(f"model.{k}: in the checkpoint, but the model has none")
+        for k, kind in (("step_count", int), ("epoch", int), ("lr", float)):
+            if not isinstance(state.get("optimizer", {}).get(k), kind):
+                problems.append(f"optimizer.{k}: missing")
+        for k in ("rng_seed", "next_step"):
+            if not isinstance(state.get(k), int):
+                problems.append(f"{k}: missing")
+        rng = [("torch_rng_state", True)] + [("cuda_rng_state", m.flat_params().is_cuda)]
+        for k, needed in rng:
+            if needed and not (isinstance(state.get(k), torch.Tensor) and state[k].dtype == torch.uint8):
+                problems.append(f"{k}: missing")
+        if self.graph is not None and isinstance(state.get("rng_seed"), int) and state["rng_seed"] != self._rng_seed:
+            problems.append("rng_seed: this trainer's captured step holds its own jitter seed as a constant; load the "
+                            "checkpoint into a new Trainer, before its first step")
+        if problems:
+            raise ValueError("the checkpoint does not fit this trainer (nothing was loaded): " + "; ".join(problems))
+        diff = checkpoint.signature_diff(state.get("hparams", {}), self.h)
+        if diff:
+            warnings.warn("hyper-parameters differ from the checkpoint's (the trainer's own are used): " + "; ".join(diff))
+        if not has_pose and dataset is not None and "dataset_signature" in state:
+            diff = checkpoint.signature_diff(state["dataset_signature"], checkpoint.dataset_signature(dataset))
+            if diff:
+                warnings.warn("the dataset differs from the checkpoint's (its draws will not continue the saved run): "
+                              + "; ".join(diff))
+        # ---- nothing has changed up to here ----
+        with torch.no_grad():
+            for dst, src in plan:
+                dst.copy_(src)
+            m.flat_grad().zero_()
+        self._pending = False  # (a pending step's gradient belonged to the state that was replaced)
+        if has_pose:
+            self.pose_opt.zero_grad()
+        o = state["optimizer"]
+        opt.step_count, opt.epoch, opt.lr = o["step_count"], o["epoch"], o["lr"]
+        self._rng_seed = state["rng_seed"]
+        torch.set_rng_state(state["torch_rng_state"].cpu())
+        if m.flat_params().is_cuda:
+            torch.cuda.set_rng_state(state["cuda_rng_state"].cpu(), m.flat_params().device)
+        m.prepare_weights()
+        self._next_step = state["next_step"]
+        return self._next_step
+
+    def save_checkpoint(self, path, dataset=None):
+        """checkpoint.save(self.state_dict(dataset), path): rank 0 writes, the other ranks (which hold
+        the same parameters) only flush their pending optimizer step and return None.  The generator
+        states in the file are rank 0's."""
+        if distributed.rank() != 0:
+            self.flush_optimizer()
+            return None
+        return checkpoint.save(self.state_dict(dataset), path)
+
+    def load_checkpoint(self, path, dataset=None):
+        """load_state_dict of the file (every rank loads it); returns its `next_step`, the
+        `start_step` of the fit that continues the run."""
+        return self.load_state_dict(checkpoint.load(path, map_location=self.model.flat_params().device), dataset)
+
+    def fit(self, dataset, n_steps, start_step=0, callback=None, callback_every=0, log_capacity=None,
+            checkpoint_every=0, checkpoint_path=None):
         """Train on `dataset` for the steps [start_step, start_step + n_steps) (step_from each) and
         return their TrainLog.
 
@@ -482,11 +651,22 @@ class Trainer:
         whenever (global_step + 1) % callback_every == 0, i.e. each time the total number of steps
         trained reaches a multiple of callback_every; flush_optimizer() has run, so the model holds
         the parameters after that step (a validation render, evaluation.evaluate_views, goes here).
-        At the end a pending deferred optimizer step is flushed."""
+        At the end a pending deferred optimizer step is flushed.
+
+        checkpoint_every > 0 with checkpoint_path: save_checkpoint(path, dataset) after the step
+        `global_step` whenever (global_step + 1) % checkpoint_every == 0, and at the end (once, if the
+        last step has just been saved).  A "{step}" in the path is replaced by the file's `next_step`
+        (global_step + 1: the steps trained, counted from step 0), one file per save; otherwise the
+        one file is replaced.  The run continues in another process with
+        fit(dataset, n, start_step=trainer.load_checkpoint(path, dataset)).  With checkpoint_every = 0
+        nothing is saved and the loop issues what it would without these arguments."""
         n_steps, start_step = int(n_steps), int(start_step)
         capacity = n_steps if log_capacity is None else int(log_capacity)
         if n_steps < 1 or capacity < 1:
             raise ValueError(f"fit: n_steps {n_steps} and log_capacity {capacity} must be at least 1")
+        checkpoint_every = int(checkpoint_every)
+        if checkpoint_every < 0 or (checkpoint_every > 0 and checkpoint_path is None):
+            raise ValueError(f"fit: checkpoint_every {checkpoint_every} needs to be >= 0, and a checkpoint_path when > 0")
         self._check_source(dataset)
         if self.graph is None:  # (a captured graph keeps the ring it was captured with)
             self._log_capacity = capacity
@@ -510,9 +690,17 @@ class Trainer:
             if callback is not None and callback_every > 0 and (s + 1) % callback_every == 0:
                 self.flush_optimizer()
                 callback(self, s)
+            if checkpoint_every > 0 and (s + 1) % checkpoint_every == 0:
+                self._save_numbered(checkpoint_path, dataset)
         self.flush_optimizer()
         self._drain(log, first, start_step + n_steps - first)
+        if checkpoint_every > 0 and (start_step + n_steps) % checkpoint_every != 0:
+            self._save_numbered(checkpoint_path, dataset)
         return log
+
+    def _save_numbered(self, path, dataset):
+        """save_checkpoint under `path` with "{step}" replaced by the next step."""
+        return self.save_checkpoint(os.fspath(path).replace("{step}", str(self._next_step)), dataset)
 
     def _drain(self, log, first_step, count):
         """The ring's rows of `count` steps into the host log: one device-to-host copy."""
