@@ -87,7 +87,7 @@ def render_rays_test(model, rays_o, rays_d, hits_t, **kwargs):
     mode = kwargs.get("test_fused", True)
     fused = bool(mode) and not model.pred_norm and not model.pred_sem and hasattr(model, "_field_fwd")
     fwd_kwargs = {k: v for k, v in kwargs.items() if k not in ("loop_stats", "test_fused")}
-    if fused and hasattr(model, "prepare_weights"):
+    if fused and N_rays > 0 and hasattr(model, "prepare_weights"):  # (no rays: nothing is launched)
         model.prepare_weights()
     if fused and mode is True and N_rays > 0:
         # the same fused iterations driven from the device (no host read per iteration)
@@ -179,13 +179,17 @@ TEST_LOOP_CHECK = 4  # iterations launched between two reads of the device loop'
 
 
 def _test_loop_device(model, rays_o, rays_d, hits_t0, alive, exp_step_factor, max_samples, min_samples, T_threshold,
-                      opacity, depth, rend, stats):
+                      opacity, depth, rend, stats, field=None):
     """render_rays_test's loop (rendering.py:68-105) with the fused iteration, its control on the
     device (ncn_test_loop_*: the alive count, N_samples and the stop test of the loop head formed by
     a kernel after each iteration); the host launches TEST_LOOP_CHECK iterations between reads of the
     done flag (iterations past the end launch empty).  Same outputs as the host-driven loop bit for
     bit: every ray's march and composite are independent of its position in the alive list.  Returns
-    total_samples (device int64)."""
+    total_samples (device int64).
+    field (test hook): replaces the ncn_field_fwd launch; called as field(xyzs, dirs, ctrl, idx, sig, rgb) with
+    the loop's buffers, it fills sig (cap) / rgb (cap, 3) for at least the slots idx[:ctrl[4]] lists; the model
+    then only supplies the marcher's grid (density_bitfield, cascades, scale, grid_size), and stats also gets
+    'ctrl' (the final control block as a list) and 'alive_last' (the buffer the last round's kept rays lead)."""
     from ._lib import call
     R, dev = rays_o.shape[0], rays_o.device
     cap = R * min_samples
@@ -194,8 +198,9 @@ def _test_loop_device(model, rays_o, rays_d, hits_t0, alive, exp_step_factor, ma
     sig, rgb = f(cap), f(cap, 3)
     n_eff = torch.empty(R, dtype=torch.int32, device=dev)
     idx = torch.empty(cap, dtype=torch.int32, device=dev)
-    model._packed_fresh = True
-    packed = model._take_packed()  # (packed before the loop: the weights do not change in it)
+    if field is None:
+        model._packed_fresh = True
+        packed = model._take_packed()  # (packed before the loop: the weights do not change in it)
     bufs = [alive, torch.empty(R, dtype=torch.int64, device=dev)]
     # the loop head's N_samples = max(min(N_rays // N_alive, 64), min_samples) (rendering.py:69-70); on
     # the first iteration N_alive == N_rays, so it is max(1, min_samples); test_loop_next forms the rest
@@ -213,8 +218,11 @@ def _test_loop_device(model, rays_o, rays_d, hits_t0, alive, exp_step_factor, ma
                  int(max_samples), ctrl, xyzs, dirs, deltas, ts, n_eff)
             call("ncn_test_loop_index", n_eff, R, ctrl, idx)
             # the field on exactly the valid slots (order = their indices, count on the device)
-            call("ncn_field_fwd", xyzs, dirs, cap, count, idx, model.xyz_encoder.params, model._levels_ptr,
-                 model._xyz_min, model._xyz_extent, packed, model._prec, 0, sig, rgb, None)
+            if field is None:
+                call("ncn_field_fwd", xyzs, dirs, cap, count, idx, model.xyz_encoder.params, model._levels_ptr,
+                     model._xyz_min, model._xyz_extent, packed, model._prec, 0, sig, rgb, None)
+            else:
+                field(xyzs, dirs, ctrl, idx, sig, rgb)
             call("ncn_test_loop_composite", sig, rgb, None, deltas, ts, a, R,
                  ctrl, 3, T_threshold, n_eff, opacity, depth, rend)
             call("ncn_test_loop_next", a, b, R, ctrl, total, R, int(max_samples), int(min_samples))
@@ -230,6 +238,9 @@ def _test_loop_device(model, rays_o, rays_d, hits_t0, alive, exp_step_factor, ma
         stats["samples_marched"] = stats.get("samples_marched", 0) + c[7]
         stats["blocked_s"] = stats.get("blocked_s", 0.0) + blocked
         stats["launched_iterations"] = stats.get("launched_iterations", 0) + it
+        if field is not None:  # (the test hook only: loop_stats of a render() call stays plain numbers)
+            stats["ctrl"] = c
+            stats["alive_last"] = bufs[c[6] % 2]  # (the rays the last round kept lead this buffer)
     return total[0]
 
 

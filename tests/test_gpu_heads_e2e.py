@@ -67,6 +67,79 @@ def test_render_with_heads(dev, scene, test_time):
         assert torch.equal(r[k], r0[k]), k
     hit = r["norm_nn"].norm(dim=1) > 1e-6
     np.testing.assert_allclose(rn["norm_nn"][hit].norm(dim=1).cpu().numpy(), 1.0, rtol=1e-5)
+    if test_time:
+        _check_heads_against_one_composite(dev, m, b, r, kw)
+
+
+def _check_heads_against_one_composite(dev, m, b, r, kw):
+    """The values of sem / norm_nn at test time: the loop driven once by hand (vren.raymarching_test,
+    model(...), the compositor on rgb for the alive decisions) keeps every ray's samples and head outputs;
+    one ncn_composite_test_fw call over them, all 3 + 3 + K channels, must give what render() returned.
+    No ray of this model comes near opaque (asserted), so both composite the same samples; the loop
+    restarts T = 1 - opacity every round where the one call keeps the running product, so the two are
+    not the same bits: each is held to the renderer's float bound (tests/render_test_cases.py:
+    GPU_C 2^-24 (n_r + 1) max(1, max|v|)) against the float64 sums over those samples."""
+    import render_test_cases as rc
+    from ncnerf_amd import _lib, vren
+    rays_o, rays_d, ms = b["rays_o"].contiguous(), b["rays_d"].contiguous(), kw["max_samples"]
+    C = 6 + K
+    _, hits_t, _ = vren.ray_aabb_intersect(rays_o, rays_d, m.center, m.half_size, 1, near_distance=kw["near_distance"])
+    ht = hits_t[:, 0].contiguous()
+    alive = torch.arange(R, device=dev)
+    op, de, re = torch.zeros(R, device=dev), torch.zeros(R, device=dev), torch.zeros(R, 3, device=dev)
+    samples, rounds = 0, []
+    with torch.no_grad(), torch.autocast("cuda"):
+        while samples < ms and len(alive):
+            NS = max(min(R // len(alive), 64), 1)
+            samples += NS
+            xyzs, dirs, deltas, ts, n_eff = vren.raymarching_test(rays_o, rays_d, ht, alive, m.density_bitfield,
+                                                                  m.cascades, m.scale, 0.0, m.grid_size, ms, NS)
+            valid = torch.arange(NS, device=dev)[None, :] < n_eff[:, None]
+            if not bool(valid.any()):
+                break
+            out = m(xyzs[valid], dirs[valid], n_sem_cls=K, **kw)
+            sig = torch.zeros(len(alive), NS, device=dev)
+            sig[valid] = out["sigmas"].float()
+            raws = torch.zeros(len(alive), NS, C, device=dev)
+            raws[valid] = torch.cat([out["rgbs"].float(), out["norms"].float(), out["sems"].float()], dim=-1)
+            rounds.append((alive.clone(), n_eff, valid, sig, raws, deltas, ts))
+            vren.composite_test_multi_fw(sig, raws[..., :3].contiguous(), deltas, ts, ht, alive, 1e-4, n_eff, op, de, re)
+            alive = alive[alive >= 0]
+    assert torch.equal(op, r["opacity"]) and float(op.max()) < 0.99  # the hand-driven loop is the renderer's
+    n = torch.zeros(R, dtype=torch.int64, device=dev)
+    for al, n_eff, *_ in rounds:
+        n[al] += n_eff
+    S = int(n.max())
+    big = [torch.zeros(R, S, device=dev), torch.zeros(R, S, C, device=dev), torch.zeros(R, S, device=dev),
+           torch.zeros(R, S, device=dev)]
+    pos = torch.zeros(R, dtype=torch.int64, device=dev)
+    for al, n_eff, valid, *arrays in rounds:
+        rows = al[:, None].expand_as(valid)[valid]
+        cols = (pos[al][:, None] + torch.arange(valid.shape[1], device=dev)[None, :])[valid]
+        for dst, src in zip(big, arrays):
+            dst[rows, cols] = src[valid]
+        pos[al] += n_eff
+    al1 = torch.arange(R, device=dev)
+    op1, de1, re1 = torch.zeros(R, device=dev), torch.zeros(R, device=dev), torch.zeros(R, C, device=dev)
+    _lib.call("ncn_composite_test_fw", *big, al1, R, S, C, 1e-4, n.int(), op1, de1, re1)
+    # the exact sums of the same samples in float64 (no ray stops, so every sample is composited): render()'s
+    # outputs and the one call's are each held to the renderer's float bound against it
+    sig64, raws64, dl64, _ = (x.double() for x in big)
+    a64 = -torch.expm1(-sig64 * dl64) * (torch.arange(S, device=dev)[None, :] < n[:, None])
+    T64 = torch.cumprod(torch.cat([torch.ones(R, 1, dtype=torch.float64, device=dev), 1 - a64[:, :-1]], dim=1), dim=1)
+    w64 = a64 * T64
+    op64 = w64.sum(1).cpu().numpy()
+    re64 = (w64[:, :, None] * raws64).sum(1).cpu().numpy()
+    nc = n.cpu().numpy()
+    vmax = big[1].abs().amax(dim=(0, 1)).cpu().numpy()
+    assert (nc > 0).any() and float(re1[:, 3:].abs().max()) > 0
+    for label, o_, norm_, sem_ in (("render()", r["opacity"], r["norm_nn"], r["sem"]),
+                                   ("one composite call", op1, re1[:, 3:6], re1[:, 6:])):
+        need = max(rc.bound_ratio(o_.cpu().numpy(), op64, nc, 1.0),
+                   rc.bound_ratio(norm_.cpu().numpy(), re64[:, 3:6], nc, vmax[3:6]),
+                   rc.bound_ratio(sem_.cpu().numpy(), re64[:, 6:], nc, vmax[6:]))
+        print(f"heads at test time, {label} against the float64 sums: needs c = {need:.3f} (allowed {rc.GPU_C})")
+        assert need <= rc.GPU_C, (label, need)
 
 
 def test_static_render_with_heads_matches_dynamic(dev, scene):

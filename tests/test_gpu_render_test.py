@@ -4,7 +4,14 @@ in the reference's structure (test_fused=False: valid mask, host-synced count, m
 scatter back into zero-filled sigmas / rgbs; rendering.py:45-149): opacity, depth, rgb and
 total_samples bit-identical, on a random-init model (no ray terminates: the loop runs to the
 sample budget) and on a model whose densities were fitted to the room's occupancy (rays stop at the
-first surface), for full-image-shaped ray sets."""
+first surface), for full-image-shaped ray sets.
+
+Where this sits in the chain that pins the test-time image:
+  oracle loop == the renderer run with a stub field   tests/test_gpu_render_test_oracle.py (C, D), exact
+                                                      in every integer, float bound per ray
+  stub run and real run differ only in the field      the field has its own parity tests
+  real unfused == real fused (host, device)           here (image-sized ray sets) and part E of that
+                                                      file (R = 1 ... 4097, all-miss, R = 0), bit for bit"""
 import os
 import sys
 
